@@ -2,8 +2,17 @@
 """Sweep throughput benchmark (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--variant v0|corr]
-                    [--scaling weak|strong] [--time-block T] [--no-cpu-baseline]
-                    [--material-steps K]
+                    [--scaling weak|strong] [--time-block T] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--side-legs 0|1] [--material-steps K]]
+
+A plain run does what the headline needs and no more: it creates the state, warms
+up, times the K steps and prints the line (metric, value, ms_per_step, the schedule and
+the timed pass's roofline from the HIP events of the timed launches).  --dump-outputs DIR
+also writes what the timed steps computed (dump_outputs below).  Everything else -- the
+end-of-run gather and its RCCL cross-check, the side legs, the material coupling, the CPU
+baseline, the reference configurations, llnl_slab_test and the PMC traffic lookup, each
+described below -- runs only under --full, after the timed region, and adds its keys to
+the same line.
 
 Workload (SURVEY.md §8(d) "SL"): 1D slab X = 0.4 cm, N = 1e6 cells, S64
 Gauss-Legendre (M = 64), 128 energy groups per GPU on a log grid 0.001-30 keV
@@ -625,6 +634,41 @@ def run_rank(solver, p: dict, steps: int, warmup: int, world: int, device, shard
     return line, absorb, gathered
 
 
+DUMP_SEED = 20261015
+DUMP_CELLS = 16384    # cells sampled by --dump-outputs
+DUMP_BYTES = 60e6     # and the bound on what it writes in all
+
+
+def dump_outputs(outdir, gathered: dict, absorb, N: int) -> dict:
+    """--dump-outputs DIR: what the timed steps computed, as DIR/<name>.npy (float64).  The
+    state after the last timed step (run_rank completes every queued step of it) is read as a
+    caller of the library reads it: the assembled result arrays of gather_results -- phi, F,
+    phi_plus (N x G_total) and the group ends left, right and balance (G_total) -- and the
+    group-summed absorption rate (N).  The per-cell arrays are written at a fixed sample of
+    cells (seeded, sorted, the same for the same --cells and --groups; all cells when they
+    fit), listed in sample_cells.npy; phi, F and phi_plus rows and absorption entries follow
+    that order.  The workload has no random input, so two runs with the same arguments write
+    the same arrays up to what the builds compute differently.  Returns what the line
+    reports under "dump_outputs"."""
+    import torch
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    G = int(gathered["phi"].shape[1])
+    n = int(min(N, DUMP_CELLS, DUMP_BYTES // (8 * (3 * G + 2))))
+    cells = np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=n, replace=False))
+    out = {"sample_cells": cells.astype(np.float64)}
+    idx = torch.as_tensor(cells, device=gathered["phi"].device)
+    for k in ("phi", "F", "phi_plus"):
+        out[k] = gathered[k].index_select(0, idx).cpu().numpy()
+    out["absorption"] = absorb.index_select(0, idx).cpu().numpy()
+    for k in ("left", "right", "balance"):
+        out[k] = gathered[k].cpu().numpy()
+    for k, a in out.items():
+        np.save(outdir / f"{k}.npy", np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": str(outdir), "arrays": {k: list(a.shape) for k, a in out.items()},
+            "bytes": int(sum(a.size for a in out.values()) * 8), "sampled_cells": n, "cells": N}
+
+
 def side_leg(p: dict, info, world: int, device, local: int, scaling: str, tb: int, what: str,
              dirs=None) -> dict:
     """A second sweep measurement on the same shard, reported beside `value` (never as
@@ -900,92 +944,18 @@ def spawn_ranks(n: int, argv, script=None, env=None, grace_s: float = 20.0, stra
         signal.signal(signal.SIGTERM, old_term)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    # defaults: the timed region is 2 steady-state passes of the fastest block (T = 40)
-    ap.add_argument("--steps", type=int, default=0, help="timed steps (default: two passes of 40)")
-    ap.add_argument("--warmup", type=int, default=-1,
-                    help="untimed steps before timing, at least the pipeline fill (default: the fill)")
-    ap.add_argument("--variant", choices=["v0", "corr"], default="v0")
-    ap.add_argument("--scaling", choices=["weak", "strong"], default="strong")
-    ap.add_argument("--groups", type=int, default=128, help="groups per GPU (weak) or in total (strong)")
-    ap.add_argument("--cells", type=int, default=1_000_000)
-    # SURVEY §8(d)'s SL names dt = 1e-3, at which the reference's BDF2 (const_B from the full dt,
-    # solver.cpp:501) overflows the slab's state to inf within the pipeline fill; the headline is
-    # timed on a finite state, which runs ~4% slower than the overflowed one on the same box
-    # (profiles/archive/r03c_ab_finite.jsonl); dt = 1e-3 is the side leg "overflow_control".  1e-9 keeps
-    # the state finite through the longest fill (1280 steps for the 16 groups of an 8-GPU run)
-    ap.add_argument("--dt", type=float, default=1e-9,
-                    help="time step of the SL slab (default 1e-9: finite state at every GPU count)")
-    ap.add_argument("--time-block", type=int, default=0,
-                    help="full steps fused per HBM pass, dividing --steps (0: the fastest dividing it)")
-    ap.add_argument("--schedule", choices=["pipelined", "aligned"], default="pipelined",
-                    help="staggered segments (exact starts) or aligned segments with deferred correction")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--side-legs", type=int, default=1,
-                    help="1: also time the T=1 (HBM-bound) pass, the overflowing dt = 1e-3 state and the other variant")
-    ap.add_argument("--material-steps", type=int, default=3,
-                    help="timed steps of the material-coupled run reported under 'material' (0: skip)")
-    # rehearsal of the multi-rank path on a one-GPU box: every rank on cuda:0, gloo
-    ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help=argparse.SUPPRESS)
-    ap.add_argument("--share-device", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
-    try:
-        mode = launch_mode(args.gpus, os.environ)
-    except ValueError as e:
-        print(f"bench.py: {e}", file=sys.stderr)
-        sys.exit(2)
-    if mode == "spawn":  # no launcher: this process starts the ranks and touches no GPU
-        sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
-
-    import torch
-    import torch.distributed as dist
+def full_legs(args, line: dict, solver, held: list, p: dict, info, dirs, world: int, rank: int, local: int,
+              device, solver_tb: int) -> None:
+    """--full: what the benchmark measures and checks beside its headline, after the timed
+    region, each under its own key of the line.  `held` holds the gathered result arrays
+    (popped here, so that they are freed before the side legs allocate their states); the
+    headline's solver is closed on the way."""
     import rtsn
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = 0 if args.share_device else int(os.environ.get("LOCAL_RANK", "0"))
-    device = torch.device("cuda", local)
-    if world > 1:
-        torch.cuda.set_device(local)
-        if args.backend == "nccl":
-            dist.init_process_group("nccl", device_id=device)
-        else:
-            dist.init_process_group("gloo")
-
-    info = shard(args.scaling, args.groups, world, rank)
-    p = dict(slab_params(info[0], args.variant, N=args.cells), dt=args.dt)
-    dirs = direction_shard(args.scaling, args.groups, p["M"], world, rank)
-    if dirs:  # fewer groups than ranks: all groups, a block of direction pairs per rank
-        info = (args.groups, 0, args.groups)
-    solver = make_solver(p, local, info, dirs)
-    if args.time_block:
-        solver.time_block = args.time_block
-    solver.pipeline = 1 if args.schedule == "pipelined" else 0  # 1: pipelined when the run fills it
-    # exactly K timed steps: the time block is --time-block, or the fastest supported one
-    # dividing K; the handle re-sizes its segments for that block
-    steps = args.steps if args.steps > 0 else 2 * (args.time_block or DEFAULT_TIME_BLOCK)
-    tb = choose_time_block(steps, args.time_block)
-    solver.time_block = tb
-    # Warmup: at least W steps, and always whole passes that fill the pipeline (segments
-    # per line passes: every segment position running, one pass apart), so that the K timed
-    # steps are the schedule's steady state whatever W the caller asks for; the steps run
-    # are reported as "warmup" (W as "warmup_requested").
-    fill = solver.sweep_geometry()[1] * tb if solver.pipeline else tb
-    warmup = warmup_steps(args.warmup, fill, tb)
-    shards = [shard(args.scaling, args.groups, world, r)[1:] for r in range(world)]
-    solver_tb = solver.time_block
-    line, _, gathered = run_rank(solver, p, steps, warmup, world, device, info, args.scaling, shards, dirs=dirs)
-    line["warmup_requested"] = args.warmup if args.warmup >= 0 else None
+    gathered = held.pop()
     # one RCCL communicator behind the C ABI for the rest of the run (the gather cross-check
     # on N > 1 GPUs, the material leg's per-step all-reduce)
     comm, comm_error = (open_comm(world, rank, local, device) if (world > 1 or args.material_steps > 0)
                         else (None, None))
-    # environment variables the library or this script reads (test and diagnostic hooks):
-    # reported so that a run under any of them is visible in its line
-    line["rtsn_env"] = {k: v for k, v in sorted(os.environ.items()) if k.startswith("RTSN_")}
-    line["launcher"] = os.environ.get("RTSN_BENCH_LAUNCHER", "torch.distributed.run" if world > 1 else "none")
     if comm is not None:
         try:
             line["rccl_nranks"] = comm.count  # ncclCommCount behind the C ABI
@@ -1042,6 +1012,108 @@ def main():
         line["reference_config"] = reference_config_timings()
     if rank == 0:
         line["llnl_slab_test"] = llnl_slab_test_rate(line.get("reference_config"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    # defaults: the timed region is 2 steady-state passes of the fastest block (T = 40)
+    ap.add_argument("--steps", type=int, default=0, help="timed steps (default: two passes of 40)")
+    ap.add_argument("--warmup", type=int, default=-1,
+                    help="untimed steps before timing, at least the pipeline fill (default: the fill)")
+    ap.add_argument("--variant", choices=["v0", "corr"], default="v0")
+    ap.add_argument("--scaling", choices=["weak", "strong"], default="strong")
+    ap.add_argument("--groups", type=int, default=128, help="groups per GPU (weak) or in total (strong)")
+    ap.add_argument("--cells", type=int, default=1_000_000)
+    # SURVEY §8(d)'s SL names dt = 1e-3, at which the reference's BDF2 (const_B from the full dt,
+    # solver.cpp:501) overflows the slab's state to inf within the pipeline fill; the headline is
+    # timed on a finite state, which runs ~4% slower than the overflowed one on the same box
+    # (profiles/archive/r03c_ab_finite.jsonl); dt = 1e-3 is the side leg "overflow_control".  1e-9 keeps
+    # the state finite through the longest fill (1280 steps for the 16 groups of an 8-GPU run)
+    ap.add_argument("--dt", type=float, default=1e-9,
+                    help="time step of the SL slab (default 1e-9: finite state at every GPU count)")
+    ap.add_argument("--time-block", type=int, default=0,
+                    help="full steps fused per HBM pass, dividing --steps (0: the fastest dividing it)")
+    ap.add_argument("--schedule", choices=["pipelined", "aligned"], default="pipelined",
+                    help="staggered segments (exact starts) or aligned segments with deferred correction")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the gather, the side legs, the material coupling, the CPU "
+                         "baseline and the reference configurations (the three options below choose among them)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--side-legs", type=int, default=1,
+                    help="with --full, 1: also time the T=1 (HBM-bound) pass, the overflowing dt = 1e-3 state and "
+                         "the other variant")
+    ap.add_argument("--material-steps", type=int, default=3,
+                    help="with --full: timed steps of the material-coupled run reported under 'material' (0: skip)")
+    # rehearsal of the multi-rank path on a one-GPU box: every rank on cuda:0, gloo
+    ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help=argparse.SUPPRESS)
+    ap.add_argument("--share-device", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    try:
+        mode = launch_mode(args.gpus, os.environ)
+    except ValueError as e:
+        print(f"bench.py: {e}", file=sys.stderr)
+        sys.exit(2)
+    if mode == "spawn":  # no launcher: this process starts the ranks and touches no GPU
+        sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
+
+    import torch
+    import torch.distributed as dist
+    import rtsn
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = 0 if args.share_device else int(os.environ.get("LOCAL_RANK", "0"))
+    device = torch.device("cuda", local)
+    if world > 1:
+        torch.cuda.set_device(local)
+        if args.backend == "nccl":
+            dist.init_process_group("nccl", device_id=device)
+        else:
+            dist.init_process_group("gloo")
+
+    info = shard(args.scaling, args.groups, world, rank)
+    p = dict(slab_params(info[0], args.variant, N=args.cells), dt=args.dt)
+    dirs = direction_shard(args.scaling, args.groups, p["M"], world, rank)
+    if dirs:  # fewer groups than ranks: all groups, a block of direction pairs per rank
+        info = (args.groups, 0, args.groups)
+    solver = make_solver(p, local, info, dirs)
+    if args.time_block:
+        solver.time_block = args.time_block
+    solver.pipeline = 1 if args.schedule == "pipelined" else 0  # 1: pipelined when the run fills it
+    # exactly K timed steps: the time block is --time-block, or the fastest supported one
+    # dividing K; the handle re-sizes its segments for that block
+    steps = args.steps if args.steps > 0 else 2 * (args.time_block or DEFAULT_TIME_BLOCK)
+    tb = choose_time_block(steps, args.time_block)
+    solver.time_block = tb
+    # Warmup: at least W steps, and always whole passes that fill the pipeline (segments
+    # per line passes: every segment position running, one pass apart), so that the K timed
+    # steps are the schedule's steady state whatever W the caller asks for; the steps run
+    # are reported as "warmup" (W as "warmup_requested").
+    fill = solver.sweep_geometry()[1] * tb if solver.pipeline else tb
+    warmup = warmup_steps(args.warmup, fill, tb)
+    shards = [shard(args.scaling, args.groups, world, r)[1:] for r in range(world)]
+    solver_tb = solver.time_block
+    want_dump = bool(args.dump_outputs)
+    line, absorb, gathered = run_rank(solver, p, steps, warmup, world, device, info, args.scaling, shards,
+                                      gather=args.full or want_dump, dirs=dirs)
+    line["warmup_requested"] = args.warmup if args.warmup >= 0 else None
+    if want_dump and rank == 0:
+        line["dump_outputs"] = dump_outputs(args.dump_outputs, gathered, absorb, p["N"])
+    del absorb
+    if args.full:
+        held = [gathered]
+        del gathered
+        full_legs(args, line, solver, held, p, info, dirs, world, rank, local, device, solver_tb)
+    else:
+        del gathered
+        solver.close()
+    # environment variables the library or this script reads (test and diagnostic hooks):
+    # reported so that a run under any of them is visible in its line
+    line["rtsn_env"] = {k: v for k, v in sorted(os.environ.items()) if k.startswith("RTSN_")}
+    line["launcher"] = os.environ.get("RTSN_BENCH_LAUNCHER", "torch.distributed.run" if world > 1 else "none")
     if rank == 0:
         line["process_wall_s"] = time.perf_counter() - T_PROCESS0
         print(json.dumps(line), flush=True)

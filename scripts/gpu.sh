@@ -4,10 +4,10 @@
 # leaves its logs in gpurun_out/TAG_*.  Steps:
 #   tests[=PYTEST_ARGS]   pytest -m gpu (all, or e.g. tests=tests/test_wavefront_gpu.py)
 #   smoke                 __graft_entry__.smoke()
-#   bench[=ARGS]          python bench.py ARGS (default: the driver's --steps 20 --warmup 5) -> TAG_bench.json
+#   bench[=ARGS]          python bench.py --full ARGS (default: --steps 20 --warmup 5; every leg) -> TAG_bench.json
 #   rehearsal             the 2-rank bench on the one GPU over gloo -> TAG_rehearsal2.json
 #   spawn2, spawn4        the same with no launcher: bench.py --gpus 2|4 starts its ranks -> TAG_spawnN.json
-#   kt[=ARGS]             rocprofv3 kernel trace + stats of bench.py ARGS (no side legs) -> TAG_kernel_stats.csv,
+#   kt[=ARGS]             rocprofv3 kernel trace + stats of a plain bench.py ARGS (headline only) -> TAG_kernel_stats.csv,
 #                         TAG_trace_summary.json
 #   pmc[=ARGS]            the four PMC passes of the headline pass -> profiles/pmc_TAG_v0_t20.json
 #   py=SCRIPT[:ARGS]      python SCRIPT ARGS (':' separates arguments), stdout -> TAG_py_N.jsonl
@@ -22,7 +22,6 @@ mkdir -p gpurun_out
 TAG=$1
 shift
 DEF_BENCH="--steps 20 --warmup 5"
-QUIET="--no-cpu-baseline --side-legs 0 --material-steps 0"
 n=0
 for step in "$@"; do
   n=$((n + 1))
@@ -50,7 +49,7 @@ for step in "$@"; do
       ;;
     bench)
       [ -z "$arg" ] && arg=$DEF_BENCH
-      timeout -k 10 600 python -u bench.py $arg > $log 2>&1 || { tail -30 $log; exit 1; }
+      timeout -k 10 600 python -u bench.py --full $arg > $log 2>&1 || { tail -30 $log; exit 1; }
       grep "^{" $log | tail -1 > gpurun_out/${TAG}_bench.json
       python3 -c "
 import json; d=json.load(open('gpurun_out/${TAG}_bench.json')); r=d['roofline']
@@ -62,7 +61,7 @@ s = d.get('schedule', {}); print('schedule', {k: s.get(k) for k in ('end_to_end_
       # the multi-rank bench path on the box's one GPU: 2 ranks sharing cuda:0 over gloo
       # (RCCL refuses two ranks on one device) -> TAG_rehearsal2.json
       timeout -k 10 600 python -m torch.distributed.run --nnodes 1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus 2 $DEF_BENCH --backend gloo --share-device --no-cpu-baseline > $log 2>&1 \
+        --master-port 29517 bench.py --gpus 2 $DEF_BENCH --backend gloo --share-device --full --no-cpu-baseline > $log 2>&1 \
         || { tail -30 $log; exit 1; }
       grep "^{" $log | tail -1 > gpurun_out/${TAG}_rehearsal2.json
       python3 -c "
@@ -72,7 +71,7 @@ print('value', d['value'], 'n_gpus', d['n_gpus'], 'comm', d.get('rt_comm_gather'
     spawn2|spawn4)
       # no launcher: bench.py --gpus N starts the N rank processes itself (all on cuda:0, gloo)
       nr=${name#spawn}
-      timeout -k 10 600 python bench.py --gpus $nr $DEF_BENCH --backend gloo --share-device --no-cpu-baseline \
+      timeout -k 10 600 python bench.py --gpus $nr $DEF_BENCH --backend gloo --share-device --full --no-cpu-baseline \
         > $log 2>&1 || { tail -30 $log; exit 1; }
       grep "^{" $log | tail -1 > gpurun_out/${TAG}_${name}.json
       python3 -c "
@@ -83,7 +82,7 @@ print('value', d['value'], 'n_gpus', d['n_gpus'], 'launcher', d.get('launcher'),
     kt)
       [ -z "$arg" ] && arg=$DEF_BENCH
       timeout -k 10 500 rocprofv3 --kernel-trace --stats -d gpurun_out/${TAG}_kt -o run --output-format csv \
-        -- python3 bench.py $arg $QUIET > $log 2>&1 || { tail -20 $log; exit 1; }
+        -- python3 bench.py $arg > $log 2>&1 || { tail -20 $log; exit 1; }
       python3 scripts/trace_summary.py gpurun_out/${TAG}_kt/run_kernel_trace.csv gpurun_out/${TAG}_trace_summary.json
       cp gpurun_out/${TAG}_kt/run_kernel_stats.csv gpurun_out/${TAG}_kernel_stats.csv
       gzip -f gpurun_out/${TAG}_kt/run_kernel_trace.csv
@@ -96,7 +95,7 @@ print('value', d['value'], 'n_gpus', d['n_gpus'], 'launcher', d.get('launcher'),
           "GRBM_GUI_ACTIVE SQ_INSTS_SALU SQ_INSTS_VMEM SQ_INSTS_LDS"; do
         i=$((i + 1))
         timeout -k 10 -s KILL 300 rocprofv3 --pmc $pmc -d gpurun_out/${TAG}_pmc_$i -o run --output-format csv \
-          -- python3 bench.py $arg $QUIET > ${log%.log}_$i.log 2>&1 || { tail -5 ${log%.log}_$i.log; exit 1; }
+          -- python3 bench.py $arg > ${log%.log}_$i.log 2>&1 || { tail -5 ${log%.log}_$i.log; exit 1; }
       done
       python3 scripts/pmc_summary.py ${TAG}_v0_t20 gpurun_out/${TAG}_pmc_1 gpurun_out/${TAG}_pmc_2 \
         gpurun_out/${TAG}_pmc_3 gpurun_out/${TAG}_pmc_4

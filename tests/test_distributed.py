@@ -248,6 +248,39 @@ def test_time_block_choice():
         assert k % t == 0 and t in bench.SUPPORTED_TIME_BLOCKS
 
 
+def test_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the result arrays as float64 .npy at a seeded cell sample that
+    is the same from call to call, all cells when they fit, within the byte bound."""
+    N, G = 40000, 6
+    rng = np.random.default_rng(3)
+    gathered = {k: torch.from_numpy(rng.random((N, G))) for k in ("phi", "F", "phi_plus")}
+    gathered.update({k: torch.from_numpy(rng.random(G)) for k in ("left", "right", "balance")})
+    absorb = torch.from_numpy(rng.random(N))
+    info = bench.dump_outputs(tmp_path / "a", gathered, absorb, N)
+    bench.dump_outputs(tmp_path / "b", gathered, absorb, N)
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == sorted(f"{k}.npy" for k in ("sample_cells", "phi", "F", "phi_plus", "absorption",
+                                                "left", "right", "balance"))
+    a = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy")) for k, v in a.items())
+    cells = a["sample_cells"].astype(int)
+    assert len(cells) == bench.DUMP_CELLS and (np.diff(cells) > 0).all() and 0 <= cells[0] and cells[-1] < N
+    for k in ("phi", "F", "phi_plus"):
+        assert np.array_equal(a[k], gathered[k].numpy()[cells])
+    assert np.array_equal(a["absorption"], absorb.numpy()[cells])
+    assert np.array_equal(a["balance"], gathered["balance"].numpy())
+    assert info["bytes"] == sum(v.nbytes for v in a.values()) <= 64e6
+    small = bench.dump_outputs(tmp_path / "c", {k: v[:100] if v.ndim == 2 else v for k, v in gathered.items()},
+                               absorb[:100], 100)
+    assert small["sampled_cells"] == 100
+    assert np.array_equal(np.load(tmp_path / "c" / "sample_cells.npy"), np.arange(100.0))
+    # the flagship shape at every GPU count stays within the bound
+    for G_total in (128, 1024):
+        n = int(min(1_000_000, bench.DUMP_CELLS, bench.DUMP_BYTES // (8 * (3 * G_total + 2))))
+        assert 8 * (n * (3 * G_total + 2) + 3 * G_total) <= 64e6
+
+
 class OracleDirShard(OracleShard):
     """CPU stand-in for a direction-pair shard (rt_create_direction_shard): the oracle
     over all directions and groups, reporting the partial sums over its directions --

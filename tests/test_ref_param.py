@@ -11,8 +11,11 @@ the oracle's (oracle/rt_oracle.c orc_parse_prm): same values bit for bit, and
 an error status exactly where the reference terminates (std::stoi / std::stod
 throwing) or would index psi_source out of range (Eigen assert).
 """
+import hashlib
+import json
 import math
 import subprocess
+import tempfile
 from pathlib import Path
 
 import numpy as np
@@ -21,27 +24,49 @@ import pytest
 from conftest import PRM_DIR, REPO
 
 REF = REPO / "oracle" / "_ref" / "ref_param"
-
-pytestmark = pytest.mark.skipif(not REF.exists(), reason="oracle/_ref/ref_param not built (needs /root/reference)")
+# what ref_param printed for every file of this module (its "@key<TAB>value" lines, keyed by
+# the sha256 of the file's bytes): the tests read the record, so they run where the
+# reference's reader was not built, and check it against the program where it was.
+# `python tests/test_ref_param.py` records it anew (needs oracle/_ref/ref_param).
+RECORD = REPO / "tests" / "golden" / "ref_param" / "recorded.json"
 
 INTS = ("M", "G", "N", "bc_left_indicator", "bc_right_indicator", "ts_method", "max_timesteps")
 DOUBLES = ("efirst", "elast", "X", "rho", "kappa_grey", "T", "V", "dt")
 BOOLS = ("use_mg_equilib", "use_correction", "include_validation")
 
 
-def ref_parse(path: Path) -> dict:
+def ref_key(path: Path) -> str:
+    return hashlib.sha256(path.read_bytes()).hexdigest() if path.exists() else "absent"
+
+
+def ref_run(path: Path) -> list:
+    """The "@" lines of ref_param on `path`; without a final "@status" line where it threw."""
     r = subprocess.run([str(REF), str(path)], capture_output=True, text=True, timeout=30)
+    lines = [l for l in r.stdout.splitlines() if l.startswith("@")]  # not param's own "Found <key> ..." lines
+    if "@status\tok" not in lines:
+        assert r.returncode != 0 and "terminate called" in r.stderr, (r.returncode, r.stderr)
+    return lines
+
+
+_recorded = None
+
+
+def ref_parse(path: Path) -> dict:
+    global _recorded
+    if _recorded is None:
+        _recorded = json.loads(RECORD.read_text())
+    lines = _recorded.get(ref_key(path))
+    assert lines is not None, f"{path.name}: no record of the reference's reader; python tests/test_ref_param.py"
+    if REF.exists():
+        assert ref_run(path) == lines, f"{path.name}: the record differs from oracle/_ref/ref_param"
     out = {"psi": []}
-    for line in r.stdout.splitlines():
-        if not line.startswith("@"):
-            continue  # param's own "Found <key> to be true." lines
+    for line in lines:
         k, _, v = line[1:].partition("\t")
         if k.startswith("psi_source["):
             out["psi"].append(float(v))
         else:
             out[k] = v
     if out.get("status") != "ok":
-        assert r.returncode != 0 and "terminate called" in r.stderr, (r.returncode, r.stderr)
         out["status"] = "throw"
     return out
 
@@ -207,3 +232,26 @@ def test_random_prm_files(rtsn_mod, oracle_mod, tmp_path, seed):
         f = tmp_path / f"r{seed}_{i}.prm"
         f.write_bytes(_random_prm(rng).encode())
         check(f, rtsn_mod, oracle_mod)
+
+
+def record():
+    """Run oracle/_ref/ref_param on every file the tests above use and write RECORD."""
+    assert REF.exists(), f"{REF} not built: make -C oracle ref"
+    inputs = [f.read_bytes() for f in sorted(PRM_DIR.glob("*.prm"))] + [EDGE[c].encode() for c in sorted(EDGE)]
+    for seed in range(8):
+        rng = np.random.default_rng(20261018 + seed)
+        inputs += [_random_prm(rng).encode() for _ in range(40)]
+    rec = {}
+    with tempfile.TemporaryDirectory() as d:
+        f = Path(d) / "case.prm"
+        rec[ref_key(f)] = ref_run(f)  # absent
+        for data in inputs:
+            f.write_bytes(data)
+            rec[ref_key(f)] = ref_run(f)
+    RECORD.parent.mkdir(parents=True, exist_ok=True)
+    RECORD.write_text(json.dumps(rec, indent=0, sort_keys=True) + "\n")
+    print(f"{len(rec)} records -> {RECORD}")
+
+
+if __name__ == "__main__":
+    record()
