@@ -184,7 +184,8 @@ rt_status rt_get_shard(rt_solver *s, int *G_total, int *M_total, int *g_lo, int 
  * directions -- and the emission sum_c rho kappa a c T^4 dx (direction-independent).
  * sources = inflow + emission, sinks = outflow_absorption.  Any NULL skipped. */
 rt_status rt_get_balance_partials(rt_solver *s, double *inflow, double *outflow_absorption, double *emission);
-/* Group data of all G groups: e_edge (G+1), B, dBdT, kappa (G); any NULL skipped. */
+/* Group data of all G groups: e_edge (G+1), B, dBdT, kappa (G); any NULL skipped.  On a
+ * region handle (rt_create_regions) B, dBdT and kappa are region 0's. */
 rt_status rt_get_group_data(rt_solver *s, double *e_edge, double *B, double *dBdT, double *kappa);
 rt_status rt_get_quadrature(rt_solver *s, double *mu, double *wt);
 /* Solver-owned psi_source (M*G, m*G+g) after construction / equilibrium sources. */
@@ -377,6 +378,60 @@ rt_status rt_get_cell_emission(rt_solver *s, double *Beff);
  * the handle's groups of sigma_g (p_g + owed_g) -- the next sweep's payment and the rest;
  * sum it over group shards. */
 rt_status rt_get_material_transit(rt_solver *s, double *E);
+
+/* ---- multi-region slabs (beyond the reference) ----------------------------
+ * The reference's medium is uniform: one rho, one kappa_g table, one T and one dx
+ * (solver.cpp:157).  A region handle holds a slab of piecewise-constant regions, listed left
+ * to right, each with its own density, opacity, temperature and mesh width.  It always runs
+ * the short-line wavefront (rt_set_wavefront): a chain lane's C cells lie in one region and
+ * the lane holds that region's cell map, so the tick loop is the uniform chain's.  Admissible
+ * C are those of 1, 2, 4, 8 that divide every region's first cell and N; lines of up to 512
+ * cells (256 with the reflective left boundary) fit at C = 1, up to 4096 (2048) with region
+ * edges on multiples of 8. */
+typedef struct {
+  int cells;                 /* > 0 */
+  double width;              /* > 0; the region's dx = width / cells */
+  double rho, kappa_grey, T; /* as the rt_params members of the same name */
+  const double *group_kappa; /* G opacities or NULL (then kappa_grey) */
+} rt_region;
+
+/* Host only, valid without a GPU.  The chain a region handle takes: among the admissible C
+ * whose chain of N / C lanes per line (twice that with a reflective left boundary) fits
+ * max_waves (1..8) waves, the least (1000 + lanes - 1) x measured tick cost, as
+ * wavefront_plan picks for a uniform line.  RT_ERR_PARAM when no admissible C fits (or a
+ * region has cells <= 0 or width <= 0).  Any NULL output skipped. */
+rt_status rt_regions_plan(const rt_region *r, int nregions, int reflective, int max_waves, int *cells_per_lane,
+                          int *waves, int *lanes);
+/* The regions of a .prm with have_regions (num_regions, filename_regions: a table of
+ * num_regions x 5 values, one row `cells width rho kappa_grey T` per region, read from
+ * table_dir as the group tables are).  With have_group_absorption_opacities every region's
+ * group_kappa is that table (the regions then differ in rho, T and dx).  *out = NULL,
+ * *nregions = 0 for a .prm without regions.  RT_ERR_PARAM for a table of another size,
+ * cells <= 0, width <= 0 or sum cells != N.  Release with rt_regions_free. */
+rt_status rt_regions_load(const char *prm_path, const char *table_dir, rt_region **out, int *nregions);
+void rt_regions_free(rt_region *r);
+
+/* A handle on the slab of regions r[0 .. nregions).  p->N must equal sum cells (else
+ * RT_ERR_PARAM); the handle's X is sum width; p->X, p->rho, p->kappa_grey, p->T and
+ * p->group_kappa are not used.  Group edges, quadrature, scheme, dt, V, use_correction, the
+ * boundary indicators and psi_source come from p.  Every region gets its own group table
+ * (B_g, dB/dT_g, the correction constants; include_validation validates each), and every cell
+ * starts at its own region's B_g.  Stepping, rt_set_ends, group shards and the state's
+ * read-outs work as on any handle; the balance terms and rt_group_absorption_device use each
+ * cell's own rho kappa_g, dx and emission.  RT_ERR_PARAM: use_mg_equilib, or a layout with
+ * no admissible chain.  RT_ERR_STATE on a region handle: rt_material_enable,
+ * rt_set_time_block, rt_set_pipeline, rt_set_segmentation, rt_set_level_waves,
+ * rt_set_wavefront(0), rt_plan_schedule.  rt_set_wavefront_cells with a C that is not
+ * admissible falls back to the plan's; rt_set_wavefront_waves re-plans (RT_ERR_PARAM, nothing
+ * changed, when no chain fits any more).  rt_get_group_data returns region 0's B, dBdT and
+ * kappa. */
+rt_status rt_create_regions(const rt_params *p, const rt_region *r, int nregions, int g_lo, int g_hi, int device,
+                            rt_solver **out);
+/* *nregions (1 for a handle without regions) and first_cell[0 .. nregions]: region k holds the
+ * cells [first_cell[k], first_cell[k + 1]).  Any NULL skipped. */
+rt_status rt_get_regions(rt_solver *s, int *nregions, int *first_cell);
+/* Region `region`'s B, dBdT, kappa (all G groups each) and dx; any NULL skipped. */
+rt_status rt_get_region_data(rt_solver *s, int region, double *B, double *dBdT, double *kappa, double *dx);
 
 /* ---- multi-GPU: RCCL behind the ABI (one process per GPU, xGMI) -----------
  * The reference is single-process (main.cc:79-133).  Energy groups are independent for

@@ -864,6 +864,39 @@ __global__ void balance_partials_kernel(const double *phi, const double *rk, con
   part[(static_cast<size_t>(rp) * Gl + g) * 2 + 1] = e;
 }
 
+// ... on a slab of regions (rt_create_regions): each cell's own rho kappa, dx and emission,
+// through the per-cell region index; the same ranges and the same operations per cell, so
+// identical regions give the uniform kernels' sums bitwise.
+__global__ void balance_partials_regions_kernel(const double *phi, const double *rk, const double *src,
+                                                const double *dx, const int *cell_region, double *part, int Gl,
+                                                int N) {
+  const long long t = static_cast<long long>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (t >= static_cast<long long>(kBalanceParts) * Gl) return;
+  const int g = static_cast<int>(t % Gl), rp = static_cast<int>(t / Gl);
+  const int c0 = static_cast<int>(static_cast<long long>(N) * rp / kBalanceParts);
+  const int c1 = static_cast<int>(static_cast<long long>(N) * (rp + 1) / kBalanceParts);
+  double a = 0.0, e = 0.0;
+  const double *col = phi + g;
+  for (int c = c0; c < c1; ++c) {
+    const int rg = cell_region[c];
+    const double r = rk[static_cast<size_t>(rg) * Gl + g], q = src[static_cast<size_t>(rg) * Gl + g];
+    a = fma(r * col[static_cast<size_t>(c) * Gl], dx[rg], a);
+    e += q;
+  }
+  part[(static_cast<size_t>(rp) * Gl + g) * 2] = a;
+  part[(static_cast<size_t>(rp) * Gl + g) * 2 + 1] = e;
+}
+
+__global__ void group_absorption_regions_kernel(const double *phi, const double *sigma, const int *cell_region,
+                                                double *out, int Gl, int N) {
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < N; c += gridDim.x * blockDim.x) {
+    const double *sg = sigma + static_cast<size_t>(cell_region[c]) * Gl;
+    double s = 0.0;
+    for (int g = 0; g < Gl; ++g) s += sg[g] * phi[static_cast<size_t>(c) * Gl + g];
+    out[c] = s;
+  }
+}
+
 __global__ void balance_sums_kernel(const double *part, double *ab, double *sr, int Gl) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= Gl) return;
@@ -1927,6 +1960,23 @@ hipError_t launch_group_absorption(const double *phi, const double *sigma, doubl
                                    hipStream_t st) {
   hipLaunchKernelGGL(group_absorption_kernel, dim3(grid_for(static_cast<size_t>(g.N), 256)), dim3(256), 0, st, phi,
                      sigma, out, g.Gl, g.N);
+  return hipGetLastError();
+}
+
+hipError_t launch_balance_sums_regions(const double *phi, const double *rk, const double *src, const double *dx,
+                                       const int *cell_region, double *part, double *ab, double *sr, int Gl, int N,
+                                       hipStream_t st) {
+  const long long lanes = static_cast<long long>(kBalanceParts) * Gl;
+  hipLaunchKernelGGL(balance_partials_regions_kernel, dim3(static_cast<unsigned>((lanes + 255) / 256)), dim3(256), 0,
+                     st, phi, rk, src, dx, cell_region, part, Gl, N);
+  hipLaunchKernelGGL(balance_sums_kernel, dim3((Gl + 63) / 64), dim3(64), 0, st, part, ab, sr, Gl);
+  return hipGetLastError();
+}
+
+hipError_t launch_group_absorption_regions(const double *phi, const double *sigma, const int *cell_region,
+                                           double *out, const Geometry &g, hipStream_t st) {
+  hipLaunchKernelGGL(group_absorption_regions_kernel, dim3(grid_for(static_cast<size_t>(g.N), 256)), dim3(256), 0, st,
+                     phi, sigma, cell_region, out, g.Gl, g.N);
   return hipGetLastError();
 }
 

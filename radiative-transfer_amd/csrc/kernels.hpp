@@ -61,6 +61,10 @@ struct SegArgs {
   double *phi;                // nullptr: not fused (phi from moments_kernel after a finalize)
   double *phic;               // [half][x][g] the correction's share (phi_correction_kernel)
   const double *wt;           // [M] quadrature weights
+  // multi-region slabs (kernels_wave.hip, the REG forms only): map is then
+  // [nregions][2][map_count<S>][Lpad], and lane_region[half][lanes] the region chain lane j's
+  // cells lie in (the mu < 0 half's table the mirror image of the mu > 0 one)
+  const int *lane_region;     // nullptr: one medium
 };
 
 struct FoldArgs {
@@ -122,6 +126,13 @@ hipError_t launch_balance_sums(const double *phi, const double *rk, const double
                                double *ab, double *sr, int Gl, int N, hipStream_t st);
 hipError_t launch_group_absorption(const double *phi, const double *sigma, double *out, const Geometry &g,
                                    hipStream_t st);
+// the same two read-outs on a slab of regions: cell c lies in region cell_region[c], with
+// rk, src, sigma [nregions][Gl] and dx [nregions] (the uniform kernels' arithmetic per cell)
+hipError_t launch_balance_sums_regions(const double *phi, const double *rk, const double *src, const double *dx,
+                                       const int *cell_region, double *part, double *ab, double *sr, int Gl, int N,
+                                       hipStream_t st);
+hipError_t launch_group_absorption_regions(const double *phi, const double *sigma, const int *cell_region,
+                                           double *out, const Geometry &g, hipStream_t st);
 
 // Planck group integrals per cell (material coupling): the algorithm of
 // Planck.cpp:44-337 in double precision on the device.

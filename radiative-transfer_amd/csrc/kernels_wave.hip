@@ -29,6 +29,7 @@
 
 #include "cell.hpp"
 #include "kernels.hpp"
+#include "wave_cost.hpp"
 
 namespace rtamd {
 
@@ -70,13 +71,19 @@ __device__ __forceinline__ constexpr bool head_redo() {
   return WIDE && C >= 8 && head_map_first<S>() < map_count<S>();
 }
 
-template <int S, int C, bool PAIR, bool REDO>
-__device__ __forceinline__ void head_maps(const SegArgs &a, int half, int ell, size_t stride, bool refl_head,
+//
+// REG (a slab of piecewise-constant regions, rtsn_regions.hip): a.map holds one map set per
+// region, [region][half][slot][Lpad], and the lane loads the set of the region its cells lie in
+// (rg, from SegArgs.lane_region); the head cell is physical cell 0, so hmap is region 0's.
+template <int S, int C, bool PAIR, bool REDO, bool REG = false>
+__device__ __forceinline__ void head_maps(const SegArgs &a, int half, int ell, size_t stride, bool refl_head, int rg,
                                           double (&W)[map_count<S>()], double (&W0)[map_count<S>()],
                                           double (&Wh)[map_count<S>()]) {
   constexpr int WN = map_count<S>(), F = head_map_first<S>();
+  const double *map = a.map;
+  if constexpr (REG) map += static_cast<size_t>(rg) * 2 * WN * stride;
 #pragma unroll
-  for (int n = 0; n < WN; ++n) W[n] = a.map[(static_cast<size_t>(half) * WN + n) * stride + ell];
+  for (int n = 0; n < WN; ++n) W[n] = map[(static_cast<size_t>(half) * WN + n) * stride + ell];
   double T[WN - F > 0 ? WN - F : 1];
 #pragma unroll
   for (int n = 0; n < WN; ++n) Wh[n] = 0.0;  // (REDO reads slots >= F only)
@@ -124,7 +131,7 @@ __device__ __forceinline__ void lane_cell(int c, bool refl_head, const double (&
 // N mod C real cells) feed nothing real -- except, with PAIR and N mod C != 0 (PAD), those of the mu < 0 line, whose exit
 // state is the mirror head's inflow: there they pass X through by a select (a per-lane
 // branch would make every tick divergent).
-template <int S, int C, bool PAIR, bool PAD>
+template <int S, int C, bool PAIR, bool PAD, bool REG = false>
 __global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, int Lw) {
   constexpr int K = SchemeDim<S>::K, WN = map_count<S>();
   const int g = threadIdx.x & 63;  // chain lane
@@ -157,7 +164,9 @@ __global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, in
   }
   const bool refl_head = PAIR && half == 1 && j == 0;  // one lane of a pair chain
   double W[WN], W0[WN], Wh[WN];
-  head_maps<S, C, PAIR, false>(a, half, ell, stride, refl_head, W, W0, Wh);
+  int rg = 0;  // the lane's region (REG); idle lanes load region 0's map
+  if constexpr (REG) rg = real ? a.lane_region[half * Lw + j] : 0;
+  head_maps<S, C, PAIR, false, REG>(a, half, ell, stride, refl_head, rg, W, W0, Wh);
 
   // Xin: the state each lane receives at its tick -- lane - 1's exit state of the same level;
   // chain lane 0's is the chain head's inflow state (solver.cpp:695-697), the mu < 0 line's
@@ -288,7 +297,7 @@ __device__ __forceinline__ constexpr int slot_pos(int r) {  // component r's dou
 // WIDE: more than 4 waves (two share a SIMD: 256 registers per lane); up to 4 waves a lane
 // has the SIMD's 512 (VGPRs + AGPRs), which the reflective pair at 8 cells per lane needs
 // (256 VGPRs + 376 B of scratch under the 8-wave bound).
-template <int S, int C, bool PAIR, bool PAD, bool WIDE>
+template <int S, int C, bool PAIR, bool PAD, bool WIDE, bool REG = false>
 __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(SegArgs a, int nsteps, int Lw) {
   constexpr int K = SchemeDim<S>::K, WN = map_count<S>();
   static_assert(K <= kChainSlot - 1, "a slot holds the carried state");
@@ -325,7 +334,9 @@ __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(
   const bool refl_head = PAIR && half == 1 && j == 0;
   constexpr bool REDO = head_redo<S, C, WIDE>();
   double W[WN], W0[WN], Wh[WN];
-  head_maps<S, C, PAIR, REDO>(a, half, ell, stride, refl_head, W, W0, Wh);  // VGPR-resident maps
+  int rg = 0;  // the lane's region (REG); idle lanes load region 0's map
+  if constexpr (REG) rg = real ? a.lane_region[half * Lw + j] : 0;
+  head_maps<S, C, PAIR, REDO, REG>(a, half, ell, stride, refl_head, rg, W, W0, Wh);  // VGPR-resident maps
   double Xin[K], X[K];
   {
     const double bv = a.bdry[static_cast<size_t>(PAIR ? 0 : half) * stride + ell];
@@ -484,8 +495,35 @@ __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(
   }
 }
 
+// Region handles (SegArgs.lane_region set): the REG forms; the plan's C divides every region
+// edge and N (regions.cpp), so no padded form.
+template <int S, bool PAIR>
+static hipError_t launch_wave_regions(const WavePlan &p, const SegArgs &a, int nsteps, int grid, hipStream_t st) {
+  const int Lw = p.lanes;
+  if (a.N % p.C != 0 || Lw * p.C != a.N) return hipErrorInvalidValue;
+  const size_t lds = sizeof(double) * kChainSlot * kChainRing * static_cast<size_t>(p.waves);
+  switch (p.C) {
+#define RT_REGION_CASE(c)                                                                                        \
+  case c:                                                                                                        \
+    if (p.waves > 4)                                                                                             \
+      hipLaunchKernelGGL((chain_kernel<S, c, PAIR, false, true, true>), dim3(grid), dim3(64 * p.waves), lds, st, a, \
+                         nsteps, Lw);                                                                            \
+    else if (p.waves > 1)                                                                                        \
+      hipLaunchKernelGGL((chain_kernel<S, c, PAIR, false, false, true>), dim3(grid), dim3(64 * p.waves), lds, st, \
+                         a, nsteps, Lw);                                                                         \
+    else                                                                                                         \
+      hipLaunchKernelGGL((wavefront_kernel<S, c, PAIR, false, true>), dim3(grid), dim3(64), 0, st, a, nsteps, Lw); \
+    break;
+    RT_REGION_CASE(1) RT_REGION_CASE(2) RT_REGION_CASE(4) RT_REGION_CASE(8)
+#undef RT_REGION_CASE
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 template <int S, bool PAIR>
 static hipError_t launch_wave_s(const WavePlan &p, const SegArgs &a, int nsteps, int grid, hipStream_t st) {
+  if (a.lane_region) return launch_wave_regions<S, PAIR>(p, a, nsteps, grid, st);
   const bool pad = PAIR && a.N % p.C != 0;
   const int Lw = p.lanes;
   if (p.waves > 1) {
@@ -529,27 +567,14 @@ static hipError_t launch_wave_s(const WavePlan &p, const SegArgs &a, int nsteps,
 
 // Which (cells per lane C, waves) a chain takes: the least estimated time of a 1000-step
 // advance, (1000 + L - 1) ticks x the measured cost of one tick at (C, waves), L the chain's
-// lanes.  Tick costs (ns, medians) from tools/chain_plan.py on chain_kernel / wavefront_kernel
-// (round 5, profiles/r05d_chain_plan.jsonl: 1000 BDF2 steps, 8 lines, every feasible C at
-// N = 16 .. 2048, vacuum and reflective; * = interpolated, no length measured there; the
-// reflective rows re-measured after the head cell took its own map, r05p_chain_plan_refl.jsonl:
-// N = 32 .. 2048 in steps filling each wave count).  A
+// lanes.  Tick costs: kTickVacuum / kTickReflective (wave_cost.hpp).  A
 // reflective pair whose N is not a multiple of C runs the padded kernel (the mu < 0 line's
 // padding cells pass the state through by a select): ~1.3x the tick (C = 4: 430 vs 346 ns at
 // one wave).  A chain's tick is ~2x a single wave's at the same C (the hand-over through LDS
 // and the per-block barrier), and beyond 4 waves two share a SIMD, so round 3's rule -- one
 // wave up to 4 cells per lane -- lost to 3 waves at C = 1 by 18% at 129 cells, and by 35% on
 // a reflective 65-cell pair.
-static const float kTickVacuum[4][kWaveMaxWaves] = {
-    {79, 141, 166, 185, 225, 248, 259, 272},     // C = 1
-    {126, 194, 217, 238, 306, 343, 356, 368},    // C = 2 (7 waves *)
-    {220, 300, 323, 341, 441, 541, 560, 579},    // C = 4 (5, 7 waves *)
-    {410, 500, 532, 555, 800, 880, 910, 943}};   // C = 8 (5-8 waves *: only C = 8 fits there)
-static const float kTickReflective[4][kWaveMaxWaves] = {  // N a multiple of C
-    {83, 156, 173, 191, 230, 255, 266, 278},     // C = 1 (round 5 before the head map: 201 .. 354)
-    {131, 203, 222, 244, 321, 349, 363, 388},    // C = 2
-    {227, 307, 330, 351, 515, 551, 570, 587},    // C = 4
-    {421, 529, 559, 579, 927, 977, 1001, 1046}};  // C = 8 (5-8 waves: the head's redo, r05t_chain_plan_c8)
+static_assert(kWaveCostWaves == kWaveMaxWaves, "wave_cost.hpp: a column per wave count");
 constexpr double kTickPadded = 1.3;
 WavePlan wavefront_plan(int N, bool reflective, int max_waves) {
   max_waves = max_waves < 1 ? 1 : (max_waves > kWaveMaxWaves ? kWaveMaxWaves : max_waves);

@@ -193,6 +193,30 @@ ParameterHandler::ParameterHandler(const std::string &filename, const std::strin
   dt_ = kv.get_double("dt", 0.00001);
   max_timesteps_ = kv.get_int("max_timesteps", 1000);
   include_validation_ = kv.get_bool("include_validation", true);
+  have_regions_ = kv.get_bool("have_regions", false);
+  if (have_regions_) {  // a slab of regions (beyond the reference): cells width rho kappa_grey T per row
+    num_regions_ = kv.get_int("num_regions", 0);
+    if (kv.status() == RT_OK && num_regions_ <= 0) {
+      fail(RT_ERR_PARAM, "have_regions: num_regions must be positive");
+    } else if (kv.status() == RT_OK) {
+      filename_regions_ = dir + kv.get_string("filename_regions", "NA");
+      if (read_table(filename_regions_, static_cast<size_t>(num_regions_) * 5, regions_) == 0) {
+        long long cells = 0;
+        for (int k = 0; k < num_regions_; ++k) {
+          const double c = regions_[5 * k], w = regions_[5 * k + 1];
+          if (!(c >= 1.0) || c > 2147483647.0 || c != static_cast<double>(static_cast<int>(c)) || !(w > 0.0)) {
+            fail(RT_ERR_PARAM, "region table " + filename_regions_ + ": row " + std::to_string(k) +
+                                   " needs a whole number of cells > 0 and a width > 0");
+            break;
+          }
+          cells += static_cast<long long>(c);
+        }
+        if (status_ == RT_OK && cells != N_)
+          fail(RT_ERR_PARAM, "region table " + filename_regions_ + ": the regions hold " + std::to_string(cells) +
+                                 " cells, N is " + std::to_string(N_));
+      }
+    }
+  }
   if (kv.status() != RT_OK) fail(kv.status(), "a numeric .prm value has no numeric prefix");
 }
 

@@ -75,6 +75,12 @@ class ParameterHandler {
   const std::vector<double> &psi_source() const { return psi_source_; }   // M*G, m*G+g
   const std::vector<double> &group_bounds() const { return group_bounds_; }
   const std::vector<double> &group_kappa() const { return group_kappa_; }
+  // beyond the reference: have_regions / num_regions / filename_regions, a table of
+  // num_regions rows `cells width rho kappa_grey T` (include/rtsn.h rt_regions_load); the
+  // reference's reader ignores the keys
+  bool get_have_regions() const { return have_regions_; }
+  int get_num_regions() const { return num_regions_; }
+  const std::vector<double> &regions() const { return regions_; }  // num_regions x 5, row-major
 
   // ParameterHandler::display_input_quantities (ParameterHandler.cpp:20-96)
   void display_input_quantities(std::ostream &os) const;
@@ -108,6 +114,10 @@ class ParameterHandler {
   int max_timesteps_ = 1000;
   bool include_validation_ = true;
   std::vector<double> psi_source_, group_bounds_, group_kappa_;
+  bool have_regions_ = false;
+  int num_regions_ = 0;
+  std::string filename_regions_;
+  std::vector<double> regions_;
 };
 
 }  // namespace rtamd

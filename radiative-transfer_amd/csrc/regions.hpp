@@ -1,0 +1,35 @@
+// regions.hpp -- host logic of the multi-region slabs (include/rtsn.h rt_regions_*,
+// rt_create_regions): which chain a slab of piecewise-constant regions takes, the per-lane and
+// per-cell region tables the kernels index, and the .prm's region table.  Plain C++, no HIP:
+// built into librtsn with the host objects and alone (tools/regions_sanitize.cpp).
+//
+// A chain lane of the short-line wavefront (kernels_wave.hip) holds C consecutive cells and one
+// cell map, so its cells must lie in one region: C is admissible when it divides every
+// region's first cell and N.  Among the admissible C whose chain fits the wave cap the plan
+// takes the least (1000 + lanes - 1) x tick cost of wave_cost.hpp, as wavefront_plan does.
+#pragma once
+
+#include <vector>
+
+#include "../../include/rtsn.h"
+
+namespace rtamd::regions {
+
+struct Plan {
+  int C = 0, waves = 0, lanes = 0;  // C = 0: no admissible chain fits
+};
+
+// first_cell[0 .. R]: region k holds the cells [first_cell[k], first_cell[k + 1]); false when a
+// region is empty or the argument is NULL
+bool first_cells(const rt_region *r, int R, std::vector<int> &first_cell);
+// bit ci set: C = 1 << ci (1, 2, 4, 8) divides every entry of first_cell
+unsigned admissible_mask(const std::vector<int> &first_cell);
+// want_C: a caller's cells per lane, taken when admissible and fitting; else the cost table's
+Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, int want_C = 0);
+// cell_region[c] for c < N
+std::vector<int> cell_table(const std::vector<int> &first_cell);
+// lane_region[half][lanes] at C cells per lane: half 1 (mu > 0) lane j holds the physical
+// cells [j C, (j + 1) C), half 0 (mu < 0) lane j the cells N - 1 - (j C + c): the mirror image
+std::vector<int> lane_table(const std::vector<int> &first_cell, int C);
+
+}  // namespace rtamd::regions

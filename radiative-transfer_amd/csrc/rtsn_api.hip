@@ -101,7 +101,7 @@ extern "C" rt_status rt_planck_groups(double T, int G, const double *e_edge, dou
 // [H + d_lo, H + d_hi) (ascending mu, mirror pairs together for the reflective BC), with
 // the full quadrature's nodes and weights and the prm psi_source rows of those directions.
 static rt_status create_impl(const rt_params *pin, int g_lo, int g_hi, int d_lo, int d_hi, int device,
-                             rt_solver **out);
+                             rt_solver **out, const rt_region *regs = nullptr, int nregs = 0);
 
 extern "C" rt_status rt_create_from_params(const rt_params *pin, int g_lo, int g_hi, int device, rt_solver **out) {
   return create_impl(pin, g_lo, g_hi, 0, 0, device, out);
@@ -115,8 +115,29 @@ extern "C" rt_status rt_create_direction_shard(const rt_params *pin, int g_lo, i
   return create_impl(pin, g_lo, g_hi, d_lo, d_hi, device, out);
 }
 
+// A slab of regions (include/rtsn.h "multi-region slabs"): the handle's X is the regions'
+// total width and its rho, kappa_grey, T, group_kappa region 0's, whatever p holds.
+extern "C" rt_status rt_create_regions(const rt_params *pin, const rt_region *r, int nregions, int g_lo, int g_hi,
+                                       int device, rt_solver **out) {
+  if (!pin || !out || !r || nregions < 1) return fail(nullptr, RT_ERR_ARG, "rt_create_regions: bad argument");
+  *out = nullptr;
+  std::vector<int> fc;
+  if (!regions::first_cells(r, nregions, fc))
+    return fail(nullptr, RT_ERR_PARAM, "regions: every region needs cells > 0 and width > 0");
+  if (fc.back() != pin->N) return fail(nullptr, RT_ERR_PARAM, "regions: N must equal the regions' cells");
+  if (pin->use_mg_equilib) return fail(nullptr, RT_ERR_PARAM, "regions: use_mg_equilib is not supported");
+  rt_params q = *pin;
+  q.X = 0.0;
+  for (int k = 0; k < nregions; ++k) q.X += r[k].width;
+  q.rho = r[0].rho;
+  q.kappa_grey = r[0].kappa_grey;
+  q.T = r[0].T;
+  q.group_kappa = r[0].group_kappa;
+  return create_impl(&q, g_lo, g_hi, 0, 0, device, out, r, nregions);
+}
+
 static rt_status create_impl(const rt_params *pin, int g_lo, int g_hi, int d_lo, int d_hi, int device,
-                             rt_solver **out) {
+                             rt_solver **out, const rt_region *regs, int nregs) {
   if (!pin || !out) return fail(nullptr, RT_ERR_ARG, "rt_create_from_params: NULL argument");
   *out = nullptr;
   const rt_params &q = *pin;
@@ -141,6 +162,7 @@ static rt_status create_impl(const rt_params *pin, int g_lo, int g_hi, int d_lo,
 
   rt_status st = phys::build_group_table(s->p, s->gt);
   if (st) return fail(nullptr, st, "group table: group edges must increase");
+  if (regs && (st = setup_regions(s.get(), regs, nregs))) return st;  // (the wave cap: after the handle's defaults)
   s->mu.resize(q.M);
   s->wt.resize(q.M);
   phys::gauss_legendre(q.M, phys::kFourPi, s->mu.data(), s->wt.data());
@@ -218,7 +240,7 @@ static rt_status create_impl(const rt_params *pin, int g_lo, int g_hi, int d_lo,
   const size_t Nrow = static_cast<size_t>(h->J) * kSweepTile;  // cells padded to whole tiles
   if (!e) e = dalloc(h->E, sizeof(double2) * 2 * Nrow * Lp);
   if (!e) e = dalloc(h->hmap, sizeof(double) * map_count_of(h->scheme) * Lp);
-  if (!e) e = dalloc(h->map, sizeof(double) * 2 * map_count_of(h->scheme) * Lp);
+  if (!e) e = dalloc(h->map, sizeof(double) * 2 * map_count_of(h->scheme) * Lp * std::max<size_t>(1, h->regions.size()));
   for (int T = 1; T <= kMaxAlignedBlock; ++T)
     if (!e) e = dalloc(h->prop[T], sizeof(double) * 2 * prop_count(K, T) * Lp);
   if (!e) e = dalloc(h->bdry, sizeof(double) * 2 * Lp);
@@ -237,6 +259,7 @@ static rt_status create_impl(const rt_params *pin, int g_lo, int g_hi, int d_lo,
   HIP_TRY(h, launch_init_state(static_cast<double2 *>(h->E.p), static_cast<const double *>(h->lineB.p), geometry(h),
                                h->stream));
   ++h->state_version;
+  if (regional(h) && (st = upload_regions(h))) return st;  // the region tables; every cell at its region's B_g
   // no host wait: the setup copies leave from the handle's pinned arena and every later call
   // is ordered after them on the stream (round 5: the create of llnl_slab_test made five
   // host round trips here and in the uploads)
@@ -259,6 +282,7 @@ extern "C" rt_status rt_set_pipeline(rt_solver *s, int on) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_pipeline: NULL handle");
   HIP_TRY(s, hipSetDevice(s->device));
   if (on < 0 || on > 2) return fail(s, RT_ERR_ARG, "rt_set_pipeline: 0 (off), 1 (auto) or 2 (always)");
+  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_pipeline: a region handle always runs the wavefront");
   if (!on && s->pipe) {
     if (rt_status st = complete(s)) return st;  // leave the positions aligned
   }
@@ -271,6 +295,7 @@ extern "C" rt_status rt_set_pipeline(rt_solver *s, int on) {
 extern "C" rt_status rt_set_wavefront(rt_solver *s, int mode) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_wavefront: NULL handle");
   if (mode < 0 || mode > 2) return fail(s, RT_ERR_ARG, "rt_set_wavefront: 0 (off), 1 (auto) or 2 (on)");
+  if (regional(s) && mode == 0) return fail(s, RT_ERR_STATE, "rt_set_wavefront: a region handle always runs the wavefront");
   if (s->wqueued) {  // steps queued for the current chain plan run on it first
     HIP_TRY(s, hipSetDevice(s->device));
     if (rt_status st = wave_flush(s)) return st;
@@ -290,6 +315,8 @@ extern "C" rt_status rt_get_wavefront(rt_solver *s, int *mode, int *active, int 
 extern "C" rt_status rt_set_wavefront_waves(rt_solver *s, int max_waves) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_wavefront_waves: NULL handle");
   if (max_waves < 1 || max_waves > kWaveMaxWaves) return fail(s, RT_ERR_ARG, "rt_set_wavefront_waves: 1..8 waves");
+  if (regional(s) && !region_wave_plan(s, max_waves).C)  // nothing changed
+    return fail(s, RT_ERR_PARAM, "rt_set_wavefront_waves: no admissible chain of the regions fits these waves");
   if (s->wqueued) {  // steps queued for the current chain plan run on it first
     HIP_TRY(s, hipSetDevice(s->device));
     if (rt_status st = wave_flush(s)) return st;
@@ -336,6 +363,7 @@ extern "C" rt_status rt_set_time_block(rt_solver *s, int steps_per_pass) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_time_block: NULL handle");
   if (!supported_time_block(steps_per_pass))
     return fail(s, RT_ERR_ARG, "rt_set_time_block: steps per pass must be 1..8, 10, 12, 16, 20, 24, 32 or 40");
+  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_time_block: a region handle always runs the wavefront");
   HIP_TRY(s, hipSetDevice(s->device));
   s->T = steps_per_pass;
   s->T_set = true;
@@ -352,6 +380,7 @@ extern "C" rt_status rt_get_time_block(rt_solver *s, int *steps_per_pass) {
 extern "C" rt_status rt_set_level_waves(rt_solver *s, int waves) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_level_waves: NULL handle");
   if (waves < 0 || waves > 4 || waves == 3) return fail(s, RT_ERR_PARAM, "rt_set_level_waves: 0 (auto), 1, 2 or 4");
+  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_level_waves: a region handle always runs the wavefront");
   HIP_TRY(s, hipSetDevice(s->device));
   s->level_waves = waves;  // segments re-sized for its occupancy before the next pass (the schedule is exact
   s->lw_set = true;        // for any segmentation)
@@ -363,6 +392,7 @@ extern "C" rt_status rt_set_level_waves(rt_solver *s, int waves) {
 extern "C" rt_status rt_set_segmentation(rt_solver *s, int wgs_per_cu) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_segmentation: NULL handle");
   if (wgs_per_cu < 0 || wgs_per_cu > 64) return fail(s, RT_ERR_ARG, "rt_set_segmentation: 0 (occupancy) .. 64");
+  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_segmentation: a region handle always runs the wavefront");
   HIP_TRY(s, hipSetDevice(s->device));
   s->seg_wgs = wgs_per_cu;
   s->seg_set = true;

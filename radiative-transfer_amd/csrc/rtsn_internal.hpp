@@ -23,6 +23,7 @@
 #include "kernels.hpp"
 #include "physics.hpp"
 #include "prm.hpp"
+#include "regions.hpp"
 
 namespace rtsn_detail {
 using namespace rtamd;
@@ -256,6 +257,21 @@ struct rt_solver {
   rtsn_detail::DeviceBuf corr_rows;           // BDF2: rows b A^j and A^64 per line (phi_correction_rows_kernel)
   bool phi_fused = false;        // angular sums fused into the coupled pass (M/2 divides 64)
   PlanckCells pc{};
+  // a slab of regions (rt_create_regions, rtsn_regions.hip): the handle then always runs the
+  // wavefront, with `map` holding one map set per region.  p.X is the regions' total width and
+  // p.rho, p.kappa_grey, p.T, gt are region 0's
+  struct Region {
+    rt_params p{};               // the handle's parameters with this region's rho, kappa_grey, T, group_kappa
+    std::vector<double> kappa;   // the region's own opacity table (p.group_kappa), if any
+    phys::GroupTable gt;
+    double dx = 0.0;
+  };
+  std::vector<Region> regions;   // empty: one medium
+  std::vector<int> first_cell;   // [regions + 1]
+  // lane_region: the chains' tables for C = 1, 2, 4, 8 back to back (lane_off[ci], -1: C not
+  // admissible); cell_region [N]; rsigma, rsrc [regions][Gl] and rdx [regions] back to back
+  rtsn_detail::DeviceBuf lane_region, cell_region, rmedium;
+  long long lane_off[4] = {-1, -1, -1, -1};
   // profiling
   bool profiling = false;
   std::vector<hipEvent_t> ev_pool;   // (start, stop) pairs of profiled launches
@@ -423,5 +439,17 @@ bool use_wavefront(const rt_solver *s);
 
 // rtsn_readout.hip
 rt_status compute_moments(rt_solver *s);
+
+// rtsn_regions.hip
+inline bool regional(const rt_solver *s) { return !s->regions.empty(); }
+rt_status setup_regions(rt_solver *s, const rt_region *r, int nregions);  // create: before the group table
+rt_status upload_regions(rt_solver *s);                                   // create: maps, tables, initial state
+WavePlan region_wave_plan(const rt_solver *s, int wave_max);
+// the region forms of line_maps_s (one map set per region into s->map, region 0's head map)
+template <int S>
+rt_status region_maps_s(rt_solver *s);
+// one medium's maps of every line: map [2][WN][Lpad], hmap [WN][Lpad] (nullptr: not wanted)
+template <int S>
+bool medium_maps(const rt_solver *s, bool unit_B, const phys::GroupTable &gt, double dx, double *map, double *hmap);
 
 }  // namespace rtsn_detail

@@ -19,24 +19,25 @@ using namespace rtsn_detail;
 // a reflective mu > 0 line and its mirror have the same l.
 static int line_direction(int H, int half, int ip) { return half == 0 ? H - 1 - ip : H + ip; }
 
-// unit_B: the source for B_g = 1 (material coupling scales it per cell)
-static LineConst line_constants(const rt_solver &s, int i, int g, bool unit_B = false) {
+// unit_B: the source for B_g = 1 (material coupling scales it per cell).  gt, dx: the medium
+// (the handle's own, or one region's: rtsn_regions.hip)
+static LineConst line_constants(const rt_solver &s, int i, int g, bool unit_B, const phys::GroupTable &gt,
+                                double dx) {
   const rt_params &p = s.p;
   const double c = phys::kLight;
-  const double dx = p.X / p.N;
   const double dt = p.dt;
   const double tau = (p.ts_method == 3) ? dt / 2.0 : dt;
   const double mu = s.mu[i], m = std::fabs(mu);
-  const double sigma = s.gt.rho[g] * s.gt.kappa[g];
+  const double sigma = gt.rho[g] * gt.kappa[g];
   LineConst L{};
   const double half = 0.5 * c * tau * dx;
   // S = 1/2 c tau dx (sigma B_g + total_correction), psi = (e_in + e_out)/2
-  L.c[LC_SC] = half * sigma * (unit_B ? 1.0 : s.gt.B[g]);
+  L.c[LC_SC] = half * sigma * (unit_B ? 1.0 : gt.B[g]);
   L.c[LC_SL] = 0.0;
   if (p.use_correction) {
     const double beta = p.V / c;
-    L.c[LC_SC] += half * ((s.gt.cor2[g] * mu) * beta - s.gt.cor3[g] * (mu * mu) * (beta * beta));
-    L.c[LC_SL] = half * s.gt.cor1[g] * mu * beta * 0.5;
+    L.c[LC_SC] += half * ((gt.cor2[g] * mu) * beta - gt.cor3[g] * (mu * mu) * (beta * beta));
+    L.c[LC_SL] = half * gt.cor1[g] * mu * beta * 0.5;
   }
   auto inverse = [](double d, double o, double &i0, double &i1) {
     const double det = d * d + o * o;
@@ -168,13 +169,11 @@ static void line_inflow(const rt_solver &s, std::vector<double> &bd) {
 // reflective chains only); unit_B: sources for B_g = 1 (material coupling), leaving
 // map_host (the propagators' source) alone.
 template <int S>
-rt_status rtsn_detail::line_maps_s(rt_solver *s, bool unit_B, DeviceBuf &map_dev, DeviceBuf &hmap_dev) {
+bool rtsn_detail::medium_maps(const rt_solver *s, bool unit_B, const phys::GroupTable &gt, double dx, double *map,
+                              double *hmap) {
   constexpr int WN = map_count<S>();
-  const double hd = 0.5 * (s->p.X / s->p.N);
+  const double hd = 0.5 * dx;
   const size_t Lp = s->Lpad;
-  std::vector<double> hmap(WN * Lp, 0.0), unit_map;
-  std::vector<double> &map = unit_B ? unit_map : s->map_host;
-  map.assign(2 * WN * Lp, 0.0);
   // lines are independent: chunks of them on the host workers (phys::parallel_for)
   const long long lines = 2LL * s->Gl * s->H;
   const int chunks = static_cast<int>(std::min<long long>(phys::host_workers(), (lines + 63) / 64));
@@ -187,10 +186,10 @@ rt_status rtsn_detail::line_maps_s(rt_solver *s, bool unit_B, DeviceBuf &map_dev
       const int gl = rem / s->H, ip = rem % s->H;
       const int i = line_direction(s->H, half, ip), g = s->g_lo + gl;
       const size_t ell = ip + static_cast<size_t>(s->H) * gl;
-      const LineConst L = line_constants(*s, i, g, unit_B);
+      const LineConst L = line_constants(*s, i, g, unit_B, gt, dx);
       if (!cell_map<S>(L, hd, half == 0, W)) bad = true;
       for (int n = 0; n < WN; ++n) map[(half * WN + n) * Lp + ell] = W[n];
-      if (half == 1) {
+      if (half == 1 && hmap) {
         double Wh[WN];
         if (!cell_map<S, true>(L, hd, false, Wh)) bad = true;
         for (int n = 0; n < head_map_first<S>(); ++n)  // the kernels keep only the rest apart
@@ -199,10 +198,39 @@ rt_status rtsn_detail::line_maps_s(rt_solver *s, bool unit_B, DeviceBuf &map_dev
       }
     }
   });
-  if (bad) return fail(s, RT_ERR_PARAM, "cell map: a structurally zero coefficient is not zero (or a head-cell row differs from its line map)");
+  return !bad;
+}
+
+template <int S>
+rt_status rtsn_detail::line_maps_s(rt_solver *s, bool unit_B, DeviceBuf &map_dev, DeviceBuf &hmap_dev) {
+  constexpr int WN = map_count<S>();
+  const size_t Lp = s->Lpad;
+  std::vector<double> hmap(WN * Lp, 0.0), unit_map;
+  std::vector<double> &map = unit_B ? unit_map : s->map_host;
+  map.assign(2 * WN * Lp, 0.0);
+  if (!medium_maps<S>(s, unit_B, s->gt, s->p.X / s->p.N, map.data(), hmap.data()))
+    return fail(s, RT_ERR_PARAM, "cell map: a structurally zero coefficient is not zero (or a head-cell row differs from its line map)");
   rt_status st;
   if ((st = upload(s, hmap_dev, hmap.data(), hmap.size() * sizeof(double)))) return st;
   if ((st = upload(s, map_dev, map.data(), map.size() * sizeof(double)))) return st;
+  return RT_OK;
+}
+
+// A slab of regions: one map set per region, [region][2][WN][Lpad], each with its own group
+// table and dx; the reflective head cell is physical cell 0, so its map is region 0's.
+template <int S>
+rt_status rtsn_detail::region_maps_s(rt_solver *s) {
+  constexpr int WN = map_count<S>();
+  const size_t Lp = s->Lpad, R = s->regions.size();
+  std::vector<double> hmap(WN * Lp, 0.0), map(R * 2 * WN * Lp, 0.0);
+  for (size_t k = 0; k < R; ++k)
+    if (!medium_maps<S>(s, false, s->regions[k].gt, s->regions[k].dx, map.data() + k * 2 * WN * Lp,
+                        k == 0 ? hmap.data() : nullptr))
+      return fail(s, RT_ERR_PARAM, "cell map: a structurally zero coefficient is not zero (or a head-cell row differs from its line map)");
+  s->map_host.assign(map.begin(), map.begin() + 2 * WN * Lp);
+  rt_status st;
+  if ((st = upload(s, s->hmap, hmap.data(), hmap.size() * sizeof(double)))) return st;
+  if ((st = upload(s, s->map, map.data(), map.size() * sizeof(double)))) return st;
   return RT_OK;
 }
 
@@ -210,7 +238,7 @@ template <int S>
 static rt_status setup_lines_s(rt_solver *s) {
   const size_t Lp = s->Lpad;
   rt_status st;
-  if ((st = line_maps_s<S>(s, false, s->map, s->hmap))) return st;
+  if ((st = regional(s) ? region_maps_s<S>(s) : line_maps_s<S>(s, false, s->map, s->hmap))) return st;
   std::vector<double> lineB(2 * Lp, 0.0);
   for (int half = 0; half < 2; ++half)
     for (int gl = 0; gl < s->Gl; ++gl)

@@ -53,6 +53,7 @@ extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
 
 extern "C" rt_status rt_material_enable(rt_solver *s, double rho_cv, const double *T_cells) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_material_enable: NULL handle");
+  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_material_enable: no material coupling on a region handle");
   if (!(rho_cv > 0.0) || !std::isfinite(rho_cv)) return fail(s, RT_ERR_ARG, "rt_material_enable: rho_cv must be > 0");
   if (s->p.use_correction && s->p.V != 0.0)
     return fail(s, RT_ERR_PARAM, "material coupling needs the v/c correction off (V = 0 or use_correction = 0)");

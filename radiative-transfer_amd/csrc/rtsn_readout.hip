@@ -320,7 +320,13 @@ static rt_status balance_sums(rt_solver *s, std::vector<double> &ab, std::vector
   HIP_TRY(s, dalloc(dbuf, sizeof(double) * (host.size() + balance_scratch_doubles(Gl))));
   double *d = static_cast<double *>(dbuf.p);
   hipError_t e = hipMemcpyAsync(d, host.data(), sizeof(double) * 2 * Gl, hipMemcpyHostToDevice, s->stream);
-  if (e == hipSuccess)
+  if (e == hipSuccess && regional(s)) {  // each cell's own rho kappa, dx and emission (rmedium: rk, src, dx)
+    const double *med = static_cast<const double *>(s->rmedium.p);
+    const size_t RG = s->regions.size() * static_cast<size_t>(Gl);
+    e = launch_balance_sums_regions(static_cast<const double *>(s->mom.p), med, med + RG, med + 2 * RG,
+                                    static_cast<const int *>(s->cell_region.p), d + host.size(), d + 2 * Gl,
+                                    d + 3 * Gl, Gl, N, s->stream);
+  } else if (e == hipSuccess)
     e = launch_balance_sums(static_cast<const double *>(s->mom.p), d, d + Gl, dx, d + host.size(), d + 2 * Gl,
                             d + 3 * Gl, Gl, N, s->stream);
   if (e == hipSuccess)
@@ -435,8 +441,14 @@ extern "C" rt_status rt_group_absorption_device(rt_solver *s, double *d_out) {
   HIP_TRY(s, hipSetDevice(s->device));
   rt_status st = compute_moments(s);
   if (st) return st;
-  HIP_TRY(s, launch_group_absorption(static_cast<const double *>(s->mom.p), static_cast<const double *>(s->sigma.p),
-                                     d_out, geometry(s), s->stream));
+  if (regional(s))
+    HIP_TRY(s, launch_group_absorption_regions(static_cast<const double *>(s->mom.p),
+                                               static_cast<const double *>(s->rmedium.p),
+                                               static_cast<const int *>(s->cell_region.p), d_out, geometry(s),
+                                               s->stream));
+  else
+    HIP_TRY(s, launch_group_absorption(static_cast<const double *>(s->mom.p), static_cast<const double *>(s->sigma.p),
+                                       d_out, geometry(s), s->stream));
   return RT_OK;
 }
 

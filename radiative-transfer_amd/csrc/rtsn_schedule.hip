@@ -11,6 +11,10 @@ using namespace rtsn_detail;
 // stepping
 // ---------------------------------------------------------------------------
 rt_status rtsn_detail::check_validation(rt_solver *s) {
+  if (s->p.include_validation)  // a slab of regions: each region's correction
+    for (size_t k = 0; k < s->regions.size(); ++k)
+      if (!phys::validate_correction(s->regions[k].p, s->regions[k].gt))
+        return fail(s, RT_ERR_VALIDATION, "validate_correction() fails in region " + std::to_string(k));
   if (s->p.include_validation && !phys::validate_correction(s->p, s->gt))
     return fail(s, RT_ERR_VALIDATION, "validate_correction() fails (correction.cpp:39-63,100-122)");
   return RT_OK;
@@ -383,6 +387,7 @@ rt_status rtsn_detail::finalize(rt_solver *s) {
 // workgroup's chain and the caller chose neither a time block nor a schedule, always with
 // rt_set_wavefront 2.
 WavePlan rtsn_detail::wave_plan(const rt_solver *s) {
+  if (regional(s)) return region_wave_plan(s, s->wave_max);
   const bool refl = s->p.bc_left_indicator == 2;
   if (s->wave_cells) {  // the caller's cells per lane, where the chain then fits wave_max waves
     const int C = s->wave_cells, lanes = (s->p.N + C - 1) / C;
@@ -399,6 +404,7 @@ WavePlan rtsn_detail::wave_plan(const rt_solver *s) {
 // SIMDs, and the segment pipeline's full-chip passes (28 FMAs per cell and level at ~90% of
 // the FP64 issue rate) carry the same work with less overhead per cell.
 bool rtsn_detail::use_wavefront(const rt_solver *s) {
+  if (regional(s)) return true;  // its only schedule
   if (s->material || s->wave == 0) return false;
   const WavePlan p = wave_plan(s);
   if (p.C == 0) return false;
@@ -427,6 +433,13 @@ rt_status rtsn_detail::wave_flush(rt_solver *s) {
   SegArgs a = seg_args(s);
   a.Gl = s->Gl;
   a.H = s->H;
+  if (regional(s)) {  // the chain's lane -> region table at the plan's cells per lane
+    const WavePlan wp = wave_plan(s);
+    int ci = 0;
+    while (ci < 3 && (1 << ci) != wp.C) ++ci;
+    if (!wp.C || s->lane_off[ci] < 0) return fail(s, RT_ERR_STATE, "regions: no admissible chain");
+    a.lane_region = static_cast<const int *>(s->lane_region.p) + s->lane_off[ci];
+  }
   while (s->wqueued > 0) {
     const int m = static_cast<int>(std::min<long long>(s->wqueued, kWaveMaxSteps));
     hipEvent_t e1;
@@ -602,6 +615,7 @@ extern "C" rt_status rt_plan_time_block(int ts_method, long long nsteps, int *st
 extern "C" rt_status rt_plan_schedule(rt_solver *s, long long nsteps, int *steps_per_pass, int *level_waves,
                                       int *wgs_per_cu, double *estimated_ms) {
   if (!s || nsteps < 0) return fail(s, RT_ERR_ARG, "rt_plan_schedule: bad argument");
+  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_plan_schedule: a region handle always runs the wavefront");
   Schedule sc;
   if (s->scheme == SCHEME_BDF2) sc = plan_schedule(run_geom(s), nsteps);
   if (steps_per_pass) *steps_per_pass = sc.T ? sc.T : s->T;

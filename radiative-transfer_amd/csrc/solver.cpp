@@ -40,15 +40,31 @@ void Solver::create(int device, const Ranks &ranks) {
   rank_ = ranks.rank;
   const rt_params p = ph_.as_params();
   const int n = ranks.nranks, r = ranks.rank, H = M_ / 2;
+  // have_regions (beyond the reference): a slab of regions, one row of the table each; the
+  // .prm's opacity table, if any, serves every region
+  std::vector<rt_region> regs;
+  if (ph_.get_have_regions()) {
+    const std::vector<double> &t = ph_.regions();
+    for (int k = 0; k < ph_.get_num_regions(); ++k)
+      regs.push_back(rt_region{static_cast<int>(t[5 * k]), t[5 * k + 1], t[5 * k + 2], t[5 * k + 3], t[5 * k + 4],
+                               p.group_kappa});
+  }
+  const int nr = static_cast<int>(regs.size());
+  auto make = [&](int lo, int hi) {
+    if (nr)
+      check(rt_create_regions(&p, regs.data(), nr, lo, hi, device, &h_), "rt_create_regions");
+    else
+      check(rt_create_from_params(&p, lo, hi, device, &h_), "rt_create_from_params");
+  };
   if (n <= 1) {
-    check(rt_create_from_params(&p, 0, 0, device, &h_), "rt_create_from_params");
+    make(0, 0);
   } else {
     if (!ranks.comm_id || r < 0 || r >= n) throw SolverError(RT_ERR_ARG, "Solver: bad rank / communicator id");
     if (G_ >= n) {
       const int lo = static_cast<int>(static_cast<long long>(r) * G_ / n);
       const int hi = static_cast<int>(static_cast<long long>(r + 1) * G_ / n);
-      check(rt_create_from_params(&p, lo, hi, device, &h_), "rt_create_from_params");
-    } else if (H >= n) {
+      make(lo, hi);
+    } else if (H >= n && !nr) {
       check(rt_create_direction_shard(&p, 0, G_, r * H / n, (r + 1) * H / n, device, &h_), "rt_create_direction_shard");
     } else {
       throw SolverError(RT_ERR_PARAM, "Solver: more ranks than groups and than direction pairs");
@@ -142,8 +158,9 @@ void Solver::moments(double *phi, double *F, double *phi_plus) {
 }
 
 void Solver::solve() {
-  if (log_ && ph_.get_validation() && (ph_.get_use_mg_equilib() || ph_.get_max_timesteps() > 0) &&
-      !validation_report()) {
+  // (a slab of regions: the library validates each region's correction in rt_solve)
+  if (log_ && ph_.get_validation() && !ph_.get_have_regions() &&
+      (ph_.get_use_mg_equilib() || ph_.get_max_timesteps() > 0) && !validation_report()) {
     // assert(validate_correction()) in computeEquilibriumSources / solve (solver.cpp:290-293, 609-612)
     log_->flush();
     std::cerr << "transfer: solver.cpp:610: void rt::Solver::solve(): Assertion `correction->validate_correction() "

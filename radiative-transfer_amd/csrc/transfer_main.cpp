@@ -194,6 +194,15 @@ int main(int argc, char **argv) {
   const int M = parameter_handler.get_M(), N = parameter_handler.get_N(), G = parameter_handler.get_G();
   std::vector<double> psi_mat, phi, F, x(N);
   for (int i = 0; i < N; i++) x[i] = (i + 0.5) * parameter_handler.get_dx();
+  if (parameter_handler.get_have_regions()) {  // cell centres of a slab of regions: each region's own dx
+    const std::vector<double> &t = parameter_handler.regions();
+    double left = 0.0;
+    for (int k = 0, c = 0; k < parameter_handler.get_num_regions(); ++k) {
+      const int cells = static_cast<int>(t[5 * k]);
+      for (int i = 0; i < cells && c < N; ++i, ++c) x[c] = left + (i + 0.5) * (t[5 * k + 1] / cells);
+      left += t[5 * k + 1];
+    }
+  }
 
   try {
     // the reference prints as it goes; RTSN_QUIET=1 keeps only the CLI's own lines

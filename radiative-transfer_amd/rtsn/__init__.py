@@ -21,4 +21,6 @@ from .api import (  # noqa: F401
     plan_time_block,
     planck_groups,
     quadrature,
+    regions_load,
+    regions_plan,
 )

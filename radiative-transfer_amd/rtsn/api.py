@@ -47,6 +47,11 @@ class rt_shard(C.Structure):
     _fields_ = [(f, C.c_int) for f in ("G", "M", "g_lo", "g_hi", "d_lo", "d_hi", "N", "reserved")]
 
 
+class rt_region(C.Structure):
+    _fields_ = [("cells", C.c_int), ("width", C.c_double), ("rho", C.c_double), ("kappa_grey", C.c_double),
+                ("T", C.c_double), ("group_kappa", C.POINTER(C.c_double))]
+
+
 _SCALARS = [f for f, _ in rt_params._fields_ if f not in ("psi_source", "group_bounds", "group_kappa")]
 
 
@@ -88,6 +93,14 @@ def lib():
         L.rt_create_from_params.argtypes = [C.POINTER(rt_params), C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
         L.rt_create_direction_shard.argtypes = [C.POINTER(rt_params), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.POINTER(vp)]
+        rp = C.POINTER(rt_region)
+        L.rt_regions_plan.argtypes = [rp, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
+        L.rt_regions_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(rp), C.POINTER(C.c_int)]
+        L.rt_regions_free.argtypes = [rp]
+        L.rt_regions_free.restype = None
+        L.rt_create_regions.argtypes = [C.POINTER(rt_params), rp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
+        L.rt_get_regions.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.rt_get_region_data.argtypes = [vp, C.c_int, dp, dp, dp, dp]
         L.rt_destroy.argtypes = [vp]
         L.rt_destroy.restype = None
         for name in ("rt_solve", "rt_synchronize", "rt_finish"):
@@ -219,6 +232,52 @@ def plan_time_block(ts_method: int, nsteps: int) -> int:
     return t.value
 
 
+def _region_structs(regions, G: int, keep: list):
+    """A list of region dicts (cells, width, rho, kappa_grey, T, group_kappa or None) as an
+    rt_region array; the opacity arrays are kept alive in `keep`."""
+    arr = (rt_region * len(regions))()
+    for k, r in enumerate(regions):
+        arr[k].cells = int(r["cells"])
+        for f in ("width", "rho", "kappa_grey", "T"):
+            setattr(arr[k], f, float(r[f]))
+        gk = r.get("group_kappa")
+        if gk is not None:
+            a = np.ascontiguousarray(gk, dtype=np.float64)
+            if a.size != G:
+                raise ValueError(f"region {k}: group_kappa must hold G = {G} opacities")
+            keep.append(a)
+            arr[k].group_kappa = _dp(a)
+    keep.append(arr)
+    return arr
+
+
+def regions_plan(regions, reflective: bool = False, max_waves: int = 8) -> dict:
+    """rt_regions_plan (host only): the wavefront chain a slab of regions takes --
+    {"cells_per_lane", "waves", "lanes"}; RtError status 3 when no admissible chain fits."""
+    keep: list = []
+    arr = _region_structs([dict(r, group_kappa=None) for r in regions], 0, keep)
+    c, w, n = C.c_int(), C.c_int(), C.c_int()
+    _check(lib().rt_regions_plan(arr, len(regions), int(bool(reflective)), int(max_waves), C.byref(c), C.byref(w),
+                                 C.byref(n)), "rt_regions_plan")
+    return {"cells_per_lane": c.value, "waves": w.value, "lanes": n.value}
+
+
+def regions_load(filename, table_dir: Optional[str] = None, G: Optional[int] = None):
+    """rt_regions_load: the regions of a .prm with have_regions as a list of dicts, or None."""
+    td = None if table_dir is None else (str(table_dir).rstrip("/") + "/").encode()
+    out, n = C.POINTER(rt_region)(), C.c_int(0)
+    _check(lib().rt_regions_load(str(filename).encode(), td, C.byref(out), C.byref(n)), "rt_regions_load")
+    if not n.value:
+        return None
+    regs = []
+    for k in range(n.value):
+        r = out[k]
+        gk = np.ctypeslib.as_array(r.group_kappa, shape=(G,)).copy() if (r.group_kappa and G) else None
+        regs.append(dict(cells=r.cells, width=r.width, rho=r.rho, kappa_grey=r.kappa_grey, T=r.T, group_kappa=gk))
+    lib().rt_regions_free(out)
+    return regs
+
+
 def planck_groups(T: float, e_edge):
     e = np.ascontiguousarray(e_edge, dtype=np.float64)
     G = len(e) - 1
@@ -245,6 +304,8 @@ class ParameterHandler:
         self.params["group_kappa"] = (np.ctypeslib.as_array(p.group_kappa, shape=(G,)).copy()
                                       if p.group_kappa else None)
         lib().rt_params_free(C.byref(p))
+        # have_regions (include/rtsn.h "multi-region slabs"): a list of region dicts, else None
+        self.regions = regions_load(filename, table_dir, G) if self.prm_found else None
 
     def __getattr__(self, name):
         # get_M(), get_G(), ... get_validation() as in ParameterHandler.h:73-98
@@ -288,15 +349,27 @@ class Solver:
     are numpy arrays in the reference's index order: psi (M, G, N), phi / F /
     phi_plus (G, N), ends (M, G, N, 2)."""
 
-    def __init__(self, ph, device: int = 0, g_lo: int = 0, g_hi: int = 0, d_lo: int = 0, d_hi: int = 0):
-        """d_hi > 0: a direction-pair shard [d_lo, d_hi) of the M/2 pairs (rt_create_direction_shard)."""
+    def __init__(self, ph, device: int = 0, g_lo: int = 0, g_hi: int = 0, d_lo: int = 0, d_hi: int = 0,
+                 regions=None):
+        """d_hi > 0: a direction-pair shard [d_lo, d_hi) of the M/2 pairs (rt_create_direction_shard).
+        regions: a slab of regions, left to right, as dicts (cells, width, rho, kappa_grey, T,
+        group_kappa or None) -- rt_create_regions; a ParameterHandler of a .prm with have_regions
+        brings its own."""
         params = ph.params if isinstance(ph, ParameterHandler) else dict(ph)
+        if regions is None and isinstance(ph, ParameterHandler):
+            regions = ph.regions
         for k, v in params_default().items():
             params.setdefault(k, v)
         keep: list = []
         p = _to_struct(params, keep)
         h = C.c_void_p()
-        if d_hi > 0:
+        if regions is not None:
+            if d_hi > 0:
+                raise ValueError("a region handle has no direction shards")
+            arr = _region_structs(regions, params["G"], keep)
+            _check(lib().rt_create_regions(C.byref(p), arr, len(regions), g_lo, g_hi, device, C.byref(h)),
+                   "rt_create_regions")
+        elif d_hi > 0:
             _check(lib().rt_create_direction_shard(C.byref(p), g_lo, g_hi, d_lo, d_hi, device, C.byref(h)),
                    "rt_create_direction_shard")
         else:
@@ -395,6 +468,12 @@ class Solver:
         self._balance = b
         return b, src, snk
 
+    def balance_partials(self):
+        """(inflow, outflow_absorption, emission) per group (rt_get_balance_partials)."""
+        i, o, e = np.empty(self.G), np.empty(self.G), np.empty(self.G)
+        _check(lib().rt_get_balance_partials(self._h, _dp(i), _dp(o), _dp(e)), "rt_get_balance_partials", self._h)
+        return i, o, e
+
     def get_balance(self) -> np.ndarray:
         return self._balance
 
@@ -418,6 +497,25 @@ class Solver:
         d = {"e_edge": np.empty(G + 1), "B": np.empty(G), "dBdT": np.empty(G), "kappa": np.empty(G)}
         _check(lib().rt_get_group_data(self._h, _dp(d["e_edge"]), _dp(d["B"]), _dp(d["dBdT"]), _dp(d["kappa"])),
                "rt_get_group_data", self._h)
+        return d
+
+    def regions(self) -> list:
+        """rt_get_regions: first_cell (regions + 1 entries; region k holds the cells
+        [first_cell[k], first_cell[k + 1])); [0, N] for a handle without regions."""
+        n = C.c_int()
+        _check(lib().rt_get_regions(self._h, C.byref(n), None), "rt_get_regions", self._h)
+        fc = (C.c_int * (n.value + 1))()
+        _check(lib().rt_get_regions(self._h, None, fc), "rt_get_regions", self._h)
+        return list(fc)
+
+    def region_data(self, r: int) -> dict:
+        """rt_get_region_data: region r's B, dBdT, kappa (all G groups) and dx."""
+        G = self.G_total
+        d = {"B": np.empty(G), "dBdT": np.empty(G), "kappa": np.empty(G)}
+        dx = C.c_double()
+        _check(lib().rt_get_region_data(self._h, int(r), _dp(d["B"]), _dp(d["dBdT"]), _dp(d["kappa"]), C.byref(dx)),
+               "rt_get_region_data", self._h)
+        d["dx"] = dx.value
         return d
 
     def quad(self):
