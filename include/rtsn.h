@@ -354,6 +354,25 @@ rt_status rt_debug_set_transfer_chunk(rt_solver *s, long long doubles);
  * (N, host) the initial T(x), NULL for the uniform p.T.  The state psi is kept; nothing
  * is owed.  (RT_WARN_UNSTABLE is no longer returned: the update is implicit in T.) */
 rt_status rt_material_enable(rt_solver *s, double rho_cv, const double *T_cells);
+/* Coupling on a region handle (rt_create_regions): rho_cv[k] > 0 is region k's heat capacity
+ * (nregions must be the handle's, else RT_ERR_ARG, as a non-positive or non-finite
+ * rho_cv[k]); T_cells (N, host) the initial T(x), NULL: every cell at its region's T.  The
+ * v/c correction must be inactive (RT_ERR_PARAM).  On a handle without regions nregions must
+ * be 1, and the call is rt_material_enable(s, rho_cv[0], T_cells).
+ * Steps 1-4 above then hold per cell with the cell's own medium: sigma_g(x) = rho(x)
+ * kappa_g(x) in the sweep, in q(x), b(x) and S(T), rho_cv(x) in the update (the same start,
+ * stop rule and iteration cap on the Newton path) and dx(x) in the mesh; the BE energy
+ * statement becomes sum_x dx(x) (sum_g phi_g / c + rho_cv(x) T + rt_get_material_transit).
+ * Every other rt_material_* call, the material getters, group shards ([q, b] summed by the
+ * caller or by rt_comm_material_step) work as on a plain coupled handle; rt_material_stability
+ * returns the largest of dt W sum_g sigma_{r,g} dB_g/dT(T_max,r) / rho_cv_r over the regions
+ * r, T_max,r region r's hottest cell.  The coupled step is one launch of the wavefront chain
+ * (one step: all fill), so the chain is re-planned for nsteps = 1 (rt_regions_plan_steps;
+ * rt_set_wavefront_cells still overrides, rt_get_wavefront reports it); results do not depend
+ * on the cells per lane, bitwise.  phi comes from the moments kernels after each step.
+ * The balance read-outs (rt_get_balance*) are not part of the coupling on any handle: their
+ * emission term uses the configured T (a region's T), not T(x). */
+rt_status rt_material_enable_regions(rt_solver *s, const double *rho_cv, int nregions, const double *T_cells);
 /* The emission's stiffness at the current T(x): number = dt W sum_g rho kappa_g
  * dB_g/dT(T_max) / rho_cv over ALL G groups (a shard reports the whole configuration's
  * number); the implicit update scales the explicit change by 1 / (1 + number) at the
@@ -402,6 +421,12 @@ typedef struct {
  * region has cells <= 0 or width <= 0).  Any NULL output skipped. */
 rt_status rt_regions_plan(const rt_region *r, int nregions, int reflective, int max_waves, int *cells_per_lane,
                           int *waves, int *lanes);
+/* The same rule for launches of nsteps >= 1 steps (else RT_ERR_ARG): the least (nsteps + lanes
+ * - 1) x tick cost.  rt_regions_plan is nsteps = 1000; a material-coupled region handle, whose
+ * launches are single steps, takes nsteps = 1 (the cost lanes x tick then favours many cells
+ * per lane wherever the tick table says so). */
+rt_status rt_regions_plan_steps(const rt_region *r, int nregions, int reflective, int max_waves, long long nsteps,
+                                int *cells_per_lane, int *waves, int *lanes);
 /* The regions of a .prm with have_regions (num_regions, filename_regions: a table of
  * num_regions x 5 values, one row `cells width rho kappa_grey T` per region, read from
  * table_dir as the group tables are).  With have_group_absorption_opacities every region's
@@ -419,7 +444,8 @@ void rt_regions_free(rt_region *r);
  * starts at its own region's B_g.  Stepping, rt_set_ends, group shards and the state's
  * read-outs work as on any handle; the balance terms and rt_group_absorption_device use each
  * cell's own rho kappa_g, dx and emission.  RT_ERR_PARAM: use_mg_equilib, or a layout with
- * no admissible chain.  RT_ERR_STATE on a region handle: rt_material_enable,
+ * no admissible chain.  RT_ERR_STATE on a region handle: rt_material_enable (material
+ * coupling is rt_material_enable_regions, one heat capacity per region),
  * rt_set_time_block, rt_set_pipeline, rt_set_segmentation, rt_set_level_waves,
  * rt_set_wavefront(0), rt_plan_schedule.  rt_set_wavefront_cells with a C that is not
  * admissible falls back to the plan's; rt_set_wavefront_waves re-plans (RT_ERR_PARAM, nothing

@@ -1041,7 +1041,11 @@ constexpr double kPlanckPre = 2.0 / ((4.141895e-10 * 4.141895e-10 * 4.141895e-10
 // and stages the tiles in LDS to write them back as contiguous [x][g] rows.  Four waves
 // per SIMD (127 VGPRs, 36 KB of LDS per block, 32-group tiles): the exp and series chains
 // are latency-bound at two (SL coupled step: 5.95 -> 4.52 ms, profiles/r06t_material_kernels.json).
+//
+// REG (a slab of regions, PlanckCells.cell_region set): bpart uses the cell's own opacities,
+// sigma_gl(x) = rsigma[cell_region[x]][gl]; nothing else of the kernel depends on the medium.
 constexpr int kPlanckCells = 64, kPlanckGroups = 32, kPlanckThreads = 256;
+template <bool REG>
 __global__ __launch_bounds__(kPlanckThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void planck_cells_kernel(PlanckCells pc, const double *Tc, double *B) {
   __shared__ double tile[2][kPlanckCells * (kPlanckGroups + 1)];
   __shared__ double bsum[kPlanckThreads / 64][kPlanckCells];
@@ -1056,6 +1060,8 @@ __global__ __launch_bounds__(kPlanckThreads) __attribute__((amdgpu_waves_per_eu(
     const double dT = lane < nx ? pc.dTlast[x0 + lane] : 0.0;
     const bool hot = T > 0.0 && isfinite(T) && !nearly_equal(T, 0.0);
     double bacc = 0.0;  // this wave's groups of sigma_g dB_g/dT at cell lane
+    const double *sg = pc.sigma;
+    if constexpr (REG) sg = pc.rsigma + static_cast<size_t>(lane < nx ? pc.cell_region[x0 + lane] : 0) * pc.Gl;
     for (int g0 = 0; g0 < pc.Gl; g0 += kPlanckGroups) {
       const int ng = min(kPlanckGroups, pc.Gl - g0);
       __syncthreads();  // rk ready; the previous chunk's tiles written out
@@ -1078,7 +1084,7 @@ __global__ __launch_bounds__(kPlanckThreads) __attribute__((amdgpu_waves_per_eu(
         }
         tile[0][lane * (kPlanckGroups + 1) + j] = b;
         tile[1][lane * (kPlanckGroups + 1) + j] = b + pay;
-        bacc += pc.sigma[g0 + j] * db;
+        bacc += sg[g0 + j] * db;
       }
       __syncthreads();
       for (int i = threadIdx.x; i < nx * ng; i += blockDim.x) {
@@ -1597,19 +1603,23 @@ __global__ __launch_bounds__(64 * kRowsWaves) void phi_correction_rows_kernel(Se
 
 // q(x) = sum_g sigma_g (phi_g(x) - W B_g(x)), phi the sum of nparts arrays
 // [part][x][g] (the fused halves and their corrections, or one full phi):
-// one wave per cell, lanes over groups, then a butterfly over the wave
+// one wave per cell, lanes over groups, then a butterfly over the wave.  REG: sigma is
+// [nregions][Gl] and cell x reads the row of its region, sigma_g(x)
+template <bool REG>
 __global__ void material_q_kernel(const double *phi, int nparts, const double *B, const double *sigma, double W,
-                                  const double *bpart, double *q, int Gl, int N) {
+                                  const double *bpart, double *q, int Gl, int N, const int *cell_region) {
   const int lane = threadIdx.x & 63;
   const int nw = (gridDim.x * blockDim.x) >> 6;
   const size_t NG = static_cast<size_t>(N) * Gl;
   for (int x = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; x < N; x += nw) {
     const size_t o = static_cast<size_t>(x) * Gl;
+    const double *sg = sigma;
+    if constexpr (REG) sg = sigma + static_cast<size_t>(cell_region[x]) * Gl;
     double acc = 0.0;
     for (int g = lane; g < Gl; g += 64) {
       double ph = phi[o + g];
       for (int p = 1; p < nparts; ++p) ph += phi[p * NG + o + g];
-      acc += sigma[g] * (ph - W * B[o + g]);
+      acc += sg[g] * (ph - W * B[o + g]);
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if (lane == 0) {
@@ -1623,12 +1633,13 @@ __global__ void material_q_kernel(const double *phi, int nparts, const double *B
 // expressions unfused); dT kept for the next Planck pass's owed emission
 // S(T) = sum over ALL G groups of sigma_g B_g(T) and its derivative (rt_oracle.c
 // material_emission_all)
-__device__ PlanckPair material_emission_all(const PlanckCells &pc, double T, const double *rk) {
+__device__ PlanckPair material_emission_all(const PlanckCells &pc, const double *sigma_all, double T,
+                                            const double *rk) {
   double a = 0.0, d = 0.0;
   for (int g = 0; g < pc.G; ++g) {
     const PlanckPair v = cell_group_planck(pc, T, g, kPlanckPre, rk);
-    a += pc.sigma_all[g] * v.b;
-    d += pc.sigma_all[g] * v.db;
+    a += sigma_all[g] * v.b;
+    d += sigma_all[g] * v.db;
   }
   return PlanckPair{a, d};
 }
@@ -1641,14 +1652,24 @@ __device__ PlanckPair material_emission_all(const PlanckCells &pc, double T, con
 // A = q + W S(T), S over all groups -- increasing, 0 for T' <= 0: one root, bracketed in
 // [0, T + dt A / rho_cv] -- by Newton's method with bisection (rt_oracle.c material_solve_cell);
 // its owed emission grows by B_g(T') - B_g(T) here and dTlast is 0 (no dB/dT dT term).
+// REG: the cell's own heat capacity rho_cv_r[cell_region[x]] (the argument is unused) and, on
+// the Newton path, its own row of the [nregions][G] table of every group's opacity.
 constexpr double kNewtonFrac = 0.25;
+template <bool REG>
 __global__ void material_update_kernel(PlanckCells pc, double *T, const double *qb, double *dTlast, double dt,
-                                       double rho_cv, double W, int N) {
+                                       double rho_cv_one, double W, int N) {
   __shared__ double rk[65];
   if (threadIdx.x <= 64) rk[threadIdx.x] = threadIdx.x ? 1.0 / threadIdx.x : 0.0;
   __syncthreads();
   for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < N; x += gridDim.x * blockDim.x) {
     const double q = qb[x], b = qb[N + x], T0 = T[x];
+    double rho_cv = rho_cv_one;
+    const double *sigma_all = pc.sigma_all;
+    if constexpr (REG) {
+      const int rg = pc.cell_region[x];
+      rho_cv = pc.rho_cv_r[rg];
+      sigma_all = pc.rsigma_all + static_cast<size_t>(rg) * pc.G;
+    }
     double dT;
     {
 #pragma clang fp contract(off)
@@ -1660,7 +1681,7 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
       dTlast[x] = dT;
       continue;
     }
-    const PlanckPair s0 = material_emission_all(pc, T0, rk);
+    const PlanckPair s0 = material_emission_all(pc, sigma_all, T0, rk);
     const double A = q + W * s0.b;
     const double hi0 = T0 + dt * A / rho_cv;  // f(hi0) = dt W S(hi0) >= 0
     double Tn = hi0;
@@ -1684,7 +1705,7 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
       }
       Tn = t;
       for (int it = 0; it < 200; ++it) {
-        const PlanckPair sv = material_emission_all(pc, t, rk);
+        const PlanckPair sv = material_emission_all(pc, sigma_all, t, rk);
         const double f = rho_cv * (t - T0) + dt * W * sv.b - dt * A;
         if (f > 0.0) hi = t; else lo = t;
         double tn = t - f / (rho_cv + dt * W * sv.db);
@@ -1707,16 +1728,20 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
 }
 
 // E[x] = dt W sum_gl sigma_gl ((Beff - B) + owed): the energy per volume the material owes
-// the radiation (rt_get_material_transit); one wave per cell, lanes over groups
+// the radiation (rt_get_material_transit); one wave per cell, lanes over groups.  REG: sigma is
+// [nregions][Gl], the cell's region's row
+template <bool REG>
 __global__ void material_transit_kernel(const double *B, const double *Beff, const double *owed, const double *sigma,
-                                        double scale, double *E, int Gl, int N) {
+                                        double scale, double *E, int Gl, int N, const int *cell_region) {
   const int lane = threadIdx.x & 63;
   const int nw = (gridDim.x * blockDim.x) >> 6;
   for (int x = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; x < N; x += nw) {
     const size_t o = static_cast<size_t>(x) * Gl;
+    const double *sg = sigma;
+    if constexpr (REG) sg = sigma + static_cast<size_t>(cell_region[x]) * Gl;
     double acc = 0.0;
     for (int g = lane; g < Gl; g += 64)
-      acc += sigma[g] * ((Beff[o + g] - B[o + g]) + owed[static_cast<size_t>(g) * N + x]);
+      acc += sg[g] * ((Beff[o + g] - B[o + g]) + owed[static_cast<size_t>(g) * N + x]);
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if (lane == 0) E[x] = scale * acc;
   }
@@ -1981,8 +2006,11 @@ hipError_t launch_group_absorption_regions(const double *phi, const double *sigm
 }
 
 hipError_t launch_planck_cells(const PlanckCells &pc, const double *T, double *B, hipStream_t st) {
-  hipLaunchKernelGGL(planck_cells_kernel, dim3(grid_for(static_cast<size_t>(pc.N), kPlanckCells)), dim3(256), 0, st,
-                     pc, T, B);
+  const dim3 grid(grid_for(static_cast<size_t>(pc.N), kPlanckCells));
+  if (pc.cell_region)
+    hipLaunchKernelGGL(planck_cells_kernel<true>, grid, dim3(256), 0, st, pc, T, B);
+  else
+    hipLaunchKernelGGL(planck_cells_kernel<false>, grid, dim3(256), 0, st, pc, T, B);
   return hipGetLastError();
 }
 
@@ -2053,23 +2081,36 @@ hipError_t launch_phi_correction_rows(int scheme, const SegArgs &a, const double
 }
 
 hipError_t launch_material_q(const double *phi, int nparts, const double *B, const double *sigma, double W,
-                             const double *bpart, double *q, int Gl, int N, hipStream_t st) {
-  hipLaunchKernelGGL(material_q_kernel, dim3(grid_for(static_cast<size_t>(N) * 64, 256)), dim3(256), 0, st, phi, nparts,
-                     B, sigma, W, bpart, q, Gl, N);
+                             const double *bpart, double *q, int Gl, int N, hipStream_t st, const int *cell_region) {
+  const dim3 grid(grid_for(static_cast<size_t>(N) * 64, 256));
+  if (cell_region)
+    hipLaunchKernelGGL(material_q_kernel<true>, grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart, q, Gl, N,
+                       cell_region);
+  else
+    hipLaunchKernelGGL(material_q_kernel<false>, grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart, q, Gl, N,
+                       cell_region);
   return hipGetLastError();
 }
 
 hipError_t launch_material_update(const PlanckCells &pc, double *T, const double *qb, double *dTlast, double dt,
                                   double rho_cv, double W, int N, hipStream_t st) {
-  hipLaunchKernelGGL(material_update_kernel, dim3(grid_for(static_cast<size_t>(N), 256)), dim3(256), 0, st, pc, T,
-                     qb, dTlast, dt, rho_cv, W, N);
+  const dim3 grid(grid_for(static_cast<size_t>(N), 256));
+  if (pc.cell_region)
+    hipLaunchKernelGGL(material_update_kernel<true>, grid, dim3(256), 0, st, pc, T, qb, dTlast, dt, rho_cv, W, N);
+  else
+    hipLaunchKernelGGL(material_update_kernel<false>, grid, dim3(256), 0, st, pc, T, qb, dTlast, dt, rho_cv, W, N);
   return hipGetLastError();
 }
 
 hipError_t launch_material_transit(const double *B, const double *Beff, const double *owed, const double *sigma,
-                                   double scale, double *E, int Gl, int N, hipStream_t st) {
-  hipLaunchKernelGGL(material_transit_kernel, dim3(grid_for(static_cast<size_t>(N) * 64, 256)), dim3(256), 0, st, B,
-                     Beff, owed, sigma, scale, E, Gl, N);
+                                   double scale, double *E, int Gl, int N, hipStream_t st, const int *cell_region) {
+  const dim3 grid(grid_for(static_cast<size_t>(N) * 64, 256));
+  if (cell_region)
+    hipLaunchKernelGGL(material_transit_kernel<true>, grid, dim3(256), 0, st, B, Beff, owed, sigma, scale, E, Gl, N,
+                       cell_region);
+  else
+    hipLaunchKernelGGL(material_transit_kernel<false>, grid, dim3(256), 0, st, B, Beff, owed, sigma, scale, E, Gl, N,
+                       cell_region);
   return hipGetLastError();
 }
 

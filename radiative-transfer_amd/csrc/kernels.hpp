@@ -154,6 +154,13 @@ struct PlanckCells {
   double b_scale;               // 1, or 0 on a direction shard without pair 0 (b counted once)
   const double *sigma_all;      // [G] rho kappa of every group (the update's S(T), all groups)
   const double *Bcell;          // [N][Gl] B_g(T^n) (the update's full-emission cells: owed += B(T') - B(T^n))
+  // a slab of regions (rt_material_enable_regions): cell x lies in region cell_region[x] and
+  // takes that region's row of the tables; then sigma, sigma_all and the launchers' scalar
+  // rho_cv are unused.  nullptr: one medium (the kernels' uniform forms, untouched)
+  const int *cell_region;       // [N]
+  const double *rsigma;         // [nregions][Gl] rho kappa of the handle's groups
+  const double *rsigma_all;     // [nregions][G] rho kappa of every group
+  const double *rho_cv_r;       // [nregions] heat capacity
 };
 // B[N][Gl] = B_g(T(x)) and the fields above
 hipError_t launch_planck_cells(const PlanckCells &pc, const double *T, double *B, hipStream_t st);
@@ -175,16 +182,21 @@ hipError_t launch_corr_rows(int scheme, const double *map, double *rows, int Lpa
 hipError_t launch_phi_correction_rows(int scheme, const SegArgs &a, const double *rows, hipStream_t st);
 hipError_t launch_correction_power(int scheme, const double *map, double *pow, int L, int Lpad, hipStream_t st);
 // q[x] = sum_g sigma_g (phi_g(x) - W B_g(x)) over the handle's groups, phi the
-// sum of nparts [N][Gl] arrays at phi (the fused parts, or one full phi); q[N + x] = bpart[x]
+// sum of nparts [N][Gl] arrays at phi (the fused parts, or one full phi); q[N + x] = bpart[x].
+// cell_region: sigma is [nregions][Gl] and cell x takes the row cell_region[x]
 hipError_t launch_material_q(const double *phi, int nparts, const double *B, const double *sigma, double W,
-                             const double *bpart, double *q, int Gl, int N, hipStream_t st);
+                             const double *bpart, double *q, int Gl, int N, hipStream_t st,
+                             const int *cell_region = nullptr);
 // from qb = [q, b] summed over all groups: dT = dt q / (rho_cv + dt W b), T(x) += dT, dTlast = dT
 // T += dt q / (rho_cv + dt W b), or the root of the full emission where dT > T / 4 (its owed
-// emission added there, dT 0): rt_oracle.c orc_material_update
+// emission added there, dT 0): rt_oracle.c orc_material_update.  pc.cell_region set: rho_cv is
+// the cell's region's (pc.rho_cv_r) and the argument unused
 hipError_t launch_material_update(const PlanckCells &pc, double *T, const double *qb, double *dTlast, double dt,
                                   double rho_cv, double W, int N, hipStream_t st);
-// E[x] = scale sum_gl sigma[gl] ((Beff - B) + owed[gl][x]) (rt_get_material_transit)
+// E[x] = scale sum_gl sigma[gl] ((Beff - B) + owed[gl][x]) (rt_get_material_transit);
+// cell_region: as for launch_material_q
 hipError_t launch_material_transit(const double *B, const double *Beff, const double *owed, const double *sigma,
-                                   double scale, double *E, int Gl, int N, hipStream_t st);
+                                   double scale, double *E, int Gl, int N, hipStream_t st,
+                                   const int *cell_region = nullptr);
 
 }  // namespace rtamd

@@ -111,16 +111,40 @@ __device__ __forceinline__ void head_maps(const SegArgs &a, int half, int ell, s
 }
 
 // Cell c of a lane: the map (W0 for a pair chain's cell 0), and with REDO the head lane's
-// redo of the rows where its map differs (head_maps).
-template <int S, int C, bool PAIR, bool REDO>
+// redo of the rows where its map differs (head_maps).  CB (the material-coupled step): the
+// maps are stored for B_g = 1 and cs, the cell's emission, scales the constant of EVERY
+// application -- W, W0 and the head lane's redo with Wh alike.
+template <int S, int C, bool PAIR, bool REDO, bool CB = false>
 __device__ __forceinline__ void lane_cell(int c, bool refl_head, const double (&W)[map_count<S>()],
                                           const double (&W0)[map_count<S>()], const double (&Wh)[map_count<S>()],
                                           const double *X, double din, double dout, double *Xn, double &oi,
-                                          double &oo) {
+                                          double &oo, double cs = 1.0) {
   constexpr int K = SchemeDim<S>::K;
-  map_apply<S, true>(PAIR && C > 1 && c == 0 ? W0 : W, X, din, dout, Xn, oi, oo);
-  if constexpr (PAIR && REDO) {
-    if (c == 0 && refl_head) map_apply<S, true, false, false, K - 1>(Wh, X, din, dout, Xn, oi, oo);
+  if constexpr (CB) {
+    map_apply<S, true>(PAIR && C > 1 && c == 0 ? W0 : W, X, din, dout, Xn, oi, oo, cs);
+    if constexpr (PAIR && REDO) {
+      if (c == 0 && refl_head) map_apply<S, true, false, false, K - 1>(Wh, X, din, dout, Xn, oi, oo, cs);
+    }
+  } else {
+    map_apply<S, true>(PAIR && C > 1 && c == 0 ? W0 : W, X, din, dout, Xn, oi, oo);
+    if constexpr (PAIR && REDO) {
+      if (c == 0 && refl_head) map_apply<S, true, false, false, K - 1>(Wh, X, din, dout, Xn, oi, oo);
+    }
+  }
+}
+
+// CB: the emission of a lane's C cells, SegArgs.bcell[x Gl + g] with g the line's group
+// (clamped as sweep_block_kernel's bload does) and x the PHYSICAL cell -- upwind cell k of the
+// mu < 0 half is physical cell N - 1 - k.  Idle lanes and cells past N read a clamped value
+// that is never committed.
+template <int C>
+__device__ __forceinline__ void lane_emission(const SegArgs &a, int half, int ell, int j, double (&bc)[C]) {
+  const double *bl = a.bcell + min(ell / a.H, a.Gl - 1);
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const long long kl = static_cast<long long>(j) * C + c;
+    const int k = static_cast<int>(kl < a.N - 1 ? kl : a.N - 1);
+    bc[c] = bl[static_cast<size_t>(half == 0 ? a.N - 1 - k : k) * a.Gl];
   }
 }
 
@@ -131,8 +155,11 @@ __device__ __forceinline__ void lane_cell(int c, bool refl_head, const double (&
 // N mod C real cells) feed nothing real -- except, with PAIR and N mod C != 0 (PAD), those of the mu < 0 line, whose exit
 // state is the mirror head's inflow: there they pass X through by a select (a per-lane
 // branch would make every tick divergent).
-template <int S, int C, bool PAIR, bool PAD, bool REG = false>
+// CB (REG only, nsteps = 1): the material-coupled step -- a.map holds the unit-B maps and the
+// lane scales their constants by its cells' emission (lane_emission); every tick is masked.
+template <int S, int C, bool PAIR, bool PAD, bool REG = false, bool CB = false>
 __global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, int Lw) {
+  static_assert(!CB || (REG && !PAD), "the coupled step exists for region chains only");
   constexpr int K = SchemeDim<S>::K, WN = map_count<S>();
   const int g = threadIdx.x & 63;  // chain lane
   const int nl = a.H * a.Gl;
@@ -167,6 +194,8 @@ __global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, in
   int rg = 0;  // the lane's region (REG); idle lanes load region 0's map
   if constexpr (REG) rg = real ? a.lane_region[half * Lw + j] : 0;
   head_maps<S, C, PAIR, false, REG>(a, half, ell, stride, refl_head, rg, W, W0, Wh);
+  double bc[CB ? C : 1];
+  if constexpr (CB) lane_emission<C>(a, half, ell, j, bc);
 
   // Xin: the state each lane receives at its tick -- lane - 1's exit state of the same level;
   // chain lane 0's is the chain head's inflow state (solver.cpp:695-697), the mu < 0 line's
@@ -221,7 +250,10 @@ __global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, in
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         double Xn[K], oi, oo;
-        lane_cell<S, C, PAIR, false>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo);
+        if constexpr (CB)
+          lane_cell<S, C, PAIR, false, true>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo, bc[c]);
+        else
+          lane_cell<S, C, PAIR, false>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo);
         if constexpr (PAD) {
           const bool pad = j * C + c >= a.N;
 #pragma unroll
@@ -246,7 +278,7 @@ __global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, in
   const int ticks = nsteps + used - 1;
   // the unmasked ticks: every real lane at a level in [1, nsteps)
   const int u_lo = min(63, used - 1) + 1, u_hi = max(u_lo, nsteps);
-  if (u_lo < u_hi && u_hi <= ticks) {
+  if (!CB && u_lo < u_hi && u_hi <= ticks) {  // (CB: one step, no lane is ever past level 0)
     run(0, u_lo, std::true_type{});
     run(u_lo, u_hi, std::false_type{});
     run(u_hi, ticks, std::true_type{});
@@ -297,9 +329,11 @@ __device__ __forceinline__ constexpr int slot_pos(int r) {  // component r's dou
 // WIDE: more than 4 waves (two share a SIMD: 256 registers per lane); up to 4 waves a lane
 // has the SIMD's 512 (VGPRs + AGPRs), which the reflective pair at 8 cells per lane needs
 // (256 VGPRs + 376 B of scratch under the 8-wave bound).
-template <int S, int C, bool PAIR, bool PAD, bool WIDE, bool REG = false>
+// CB: the material-coupled step, as in wavefront_kernel (REG only, nsteps = 1: every block masked).
+template <int S, int C, bool PAIR, bool PAD, bool WIDE, bool REG = false, bool CB = false>
 __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(SegArgs a, int nsteps, int Lw) {
   constexpr int K = SchemeDim<S>::K, WN = map_count<S>();
+  static_assert(!CB || (REG && !PAD), "the coupled step exists for region chains only");
   static_assert(K <= kChainSlot - 1, "a slot holds the carried state");
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
@@ -337,6 +371,8 @@ __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(
   int rg = 0;  // the lane's region (REG); idle lanes load region 0's map
   if constexpr (REG) rg = real ? a.lane_region[half * Lw + j] : 0;
   head_maps<S, C, PAIR, REDO, REG>(a, half, ell, stride, refl_head, rg, W, W0, Wh);  // VGPR-resident maps
+  double bc[CB ? C : 1];
+  if constexpr (CB) lane_emission<C>(a, half, ell, j, bc);
   double Xin[K], X[K];
   {
     const double bv = a.bdry[static_cast<size_t>(PAIR ? 0 : half) * stride + ell];
@@ -374,7 +410,10 @@ __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       double Xn[K], oi, oo;
-      lane_cell<S, C, PAIR, REDO>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo);
+      if constexpr (CB)
+        lane_cell<S, C, PAIR, REDO, true>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo, bc[c]);
+      else
+        lane_cell<S, C, PAIR, REDO>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo);
       if constexpr (PAD) {
         const bool pad = j * C + c >= a.N;
 #pragma unroll
@@ -424,7 +463,7 @@ __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(
   read_slot(rd_region, nx, true);  // chain tick 0 (slot 0)
   for (int b = 0; b < nblocks; ++b) {
     const int t0 = b * kChainBlock - wsk;  // chain tick of the block's first wall tick (= 0 mod the block)
-    if (K > 1 && t0 >= u_lo && t0 + kChainBlock <= u_hi) {
+    if (!CB && K > 1 && t0 >= u_lo && t0 + kChainBlock <= u_hi) {
       // unmasked block: ring offsets fixed relative to the block's slot base
       const int base = t0 & RM, nbase = (t0 + kChainBlock) & RM;
       const double *rb = rd_region + base * kChainSlot, *rn = rd_region + nbase * kChainSlot;
@@ -496,23 +535,26 @@ __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(
 }
 
 // Region handles (SegArgs.lane_region set): the REG forms; the plan's C divides every region
-// edge and N (regions.cpp), so no padded form.
-template <int S, bool PAIR>
+// edge and N (regions.cpp), so no padded form.  CB: with SegArgs.bcell the material-coupled
+// step (one step per launch, the maps stored for B_g = 1).
+template <int S, bool PAIR, bool CB>
 static hipError_t launch_wave_regions(const WavePlan &p, const SegArgs &a, int nsteps, int grid, hipStream_t st) {
   const int Lw = p.lanes;
   if (a.N % p.C != 0 || Lw * p.C != a.N) return hipErrorInvalidValue;
+  if (CB && (nsteps != 1 || a.Gl < 1)) return hipErrorInvalidValue;
   const size_t lds = sizeof(double) * kChainSlot * kChainRing * static_cast<size_t>(p.waves);
   switch (p.C) {
 #define RT_REGION_CASE(c)                                                                                        \
   case c:                                                                                                        \
     if (p.waves > 4)                                                                                             \
-      hipLaunchKernelGGL((chain_kernel<S, c, PAIR, false, true, true>), dim3(grid), dim3(64 * p.waves), lds, st, a, \
-                         nsteps, Lw);                                                                            \
+      hipLaunchKernelGGL((chain_kernel<S, c, PAIR, false, true, true, CB>), dim3(grid), dim3(64 * p.waves), lds, \
+                         st, a, nsteps, Lw);                                                                     \
     else if (p.waves > 1)                                                                                        \
-      hipLaunchKernelGGL((chain_kernel<S, c, PAIR, false, false, true>), dim3(grid), dim3(64 * p.waves), lds, st, \
-                         a, nsteps, Lw);                                                                         \
+      hipLaunchKernelGGL((chain_kernel<S, c, PAIR, false, false, true, CB>), dim3(grid), dim3(64 * p.waves), lds, \
+                         st, a, nsteps, Lw);                                                                     \
     else                                                                                                         \
-      hipLaunchKernelGGL((wavefront_kernel<S, c, PAIR, false, true>), dim3(grid), dim3(64), 0, st, a, nsteps, Lw); \
+      hipLaunchKernelGGL((wavefront_kernel<S, c, PAIR, false, true, CB>), dim3(grid), dim3(64), 0, st, a, nsteps, \
+                         Lw);                                                                                    \
     break;
     RT_REGION_CASE(1) RT_REGION_CASE(2) RT_REGION_CASE(4) RT_REGION_CASE(8)
 #undef RT_REGION_CASE
@@ -523,7 +565,10 @@ static hipError_t launch_wave_regions(const WavePlan &p, const SegArgs &a, int n
 
 template <int S, bool PAIR>
 static hipError_t launch_wave_s(const WavePlan &p, const SegArgs &a, int nsteps, int grid, hipStream_t st) {
-  if (a.lane_region) return launch_wave_regions<S, PAIR>(p, a, nsteps, grid, st);
+  if (a.lane_region)
+    return a.bcell ? launch_wave_regions<S, PAIR, true>(p, a, nsteps, grid, st)
+                   : launch_wave_regions<S, PAIR, false>(p, a, nsteps, grid, st);
+  if (a.bcell) return hipErrorInvalidValue;  // the coupled step of one medium is the segment pass's
   const bool pad = PAIR && a.N % p.C != 0;
   const int Lw = p.lanes;
   if (p.waves > 1) {

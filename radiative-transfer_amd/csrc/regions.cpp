@@ -35,7 +35,7 @@ unsigned admissible_mask(const std::vector<int> &first_cell) {
   return mask;
 }
 
-Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, int want_C) {
+Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, int want_C, long long nsteps) {
   max_waves = max_waves < 1 ? 1 : (max_waves > kWaveCostWaves ? kWaveCostWaves : max_waves);
   if (first_cell.size() < 2 || first_cell.back() < 1) return Plan{};
   const int N = first_cell.back();
@@ -48,7 +48,8 @@ Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, in
     const int used = reflective ? 2 * Lw : Lw, waves = (used + 63) / 64;
     if (waves > max_waves) continue;
     if (C == want_C) return Plan{C, waves, Lw};
-    const double cost = (1000.0 + used - 1) * (reflective ? kTickReflective : kTickVacuum)[ci][waves - 1];
+    const double cost =
+        (static_cast<double>(nsteps) + used - 1) * (reflective ? kTickReflective : kTickVacuum)[ci][waves - 1];
     if (!best.C || cost < best_cost) {
       best = Plan{C, waves, Lw};
       best_cost = cost;
@@ -95,12 +96,18 @@ rt_status rfail(rt_status st, const std::string &msg) {
 
 extern "C" rt_status rt_regions_plan(const rt_region *r, int nregions, int reflective, int max_waves,
                                      int *cells_per_lane, int *waves, int *lanes) {
+  return rt_regions_plan_steps(r, nregions, reflective, max_waves, 1000, cells_per_lane, waves, lanes);
+}
+
+extern "C" rt_status rt_regions_plan_steps(const rt_region *r, int nregions, int reflective, int max_waves,
+                                           long long nsteps, int *cells_per_lane, int *waves, int *lanes) {
   if (!r || nregions < 1) return rfail(RT_ERR_ARG, "rt_regions_plan: NULL regions or nregions < 1");
   if (max_waves < 1 || max_waves > rtamd::kWaveCostWaves) return rfail(RT_ERR_ARG, "rt_regions_plan: 1..8 waves");
+  if (nsteps < 1) return rfail(RT_ERR_ARG, "rt_regions_plan_steps: nsteps < 1");
   std::vector<int> fc;
   if (!rtamd::regions::first_cells(r, nregions, fc))
     return rfail(RT_ERR_PARAM, "regions: every region needs cells > 0 and width > 0");
-  const rtamd::regions::Plan p = rtamd::regions::plan(fc, reflective != 0, max_waves);
+  const rtamd::regions::Plan p = rtamd::regions::plan(fc, reflective != 0, max_waves, 0, nsteps);
   if (cells_per_lane) *cells_per_lane = p.C;
   if (waves) *waves = p.waves;
   if (lanes) *lanes = p.lanes;

@@ -6,7 +6,8 @@
 // A chain lane of the short-line wavefront (kernels_wave.hip) holds C consecutive cells and one
 // cell map, so its cells must lie in one region: C is admissible when it divides every
 // region's first cell and N.  Among the admissible C whose chain fits the wave cap the plan
-// takes the least (1000 + lanes - 1) x tick cost of wave_cost.hpp, as wavefront_plan does.
+// takes the least (nsteps + lanes - 1) x tick cost of wave_cost.hpp: nsteps = 1000 as
+// wavefront_plan does, or 1 for a material-coupled handle, whose launches are single steps.
 #pragma once
 
 #include <vector>
@@ -25,7 +26,8 @@ bool first_cells(const rt_region *r, int R, std::vector<int> &first_cell);
 // bit ci set: C = 1 << ci (1, 2, 4, 8) divides every entry of first_cell
 unsigned admissible_mask(const std::vector<int> &first_cell);
 // want_C: a caller's cells per lane, taken when admissible and fitting; else the cost table's
-Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, int want_C = 0);
+Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, int want_C = 0,
+          long long nsteps = 1000);
 // cell_region[c] for c < N
 std::vector<int> cell_table(const std::vector<int> &first_cell);
 // lane_region[half][lanes] at C cells per lane: half 1 (mu > 0) lane j holds the physical

@@ -271,6 +271,10 @@ struct rt_solver {
   // lane_region: the chains' tables for C = 1, 2, 4, 8 back to back (lane_off[ci], -1: C not
   // admissible); cell_region [N]; rsigma, rsrc [regions][Gl] and rdx [regions] back to back
   rtsn_detail::DeviceBuf lane_region, cell_region, rmedium;
+  // ... with material coupling (rt_material_enable_regions): rho_cv [regions] then rho kappa of
+  // every group [regions][G] back to back; map_unit then holds one unit-B map set per region
+  rtsn_detail::DeviceBuf rmaterial;
+  std::vector<double> rho_cv_r;  // [regions] heat capacities (host copy: rt_material_stability)
   long long lane_off[4] = {-1, -1, -1, -1};
   // profiling
   bool profiling = false;
@@ -433,6 +437,7 @@ rt_status enqueue_pass(rt_solver *s, int T, bool coupled = false);
 rt_status complete(rt_solver *s);
 rt_status finalize(rt_solver *s);
 rt_status wave_flush(rt_solver *s);
+rt_status wave_coupled_pass(rt_solver *s);  // a region handle's material-coupled step (one launch)
 WavePlan wave_plan(const rt_solver *s);
 void end_plan(rt_solver *s);  // the planned schedule gives way to the handle's own
 bool use_wavefront(const rt_solver *s);
@@ -447,7 +452,7 @@ rt_status upload_regions(rt_solver *s);                                   // cre
 WavePlan region_wave_plan(const rt_solver *s, int wave_max);
 // the region forms of line_maps_s (one map set per region into s->map, region 0's head map)
 template <int S>
-rt_status region_maps_s(rt_solver *s);
+rt_status region_maps_s(rt_solver *s, bool unit_B = false);  // unit_B: into map_unit, hmap_unit
 // one medium's maps of every line: map [2][WN][Lpad], hmap [WN][Lpad] (nullptr: not wanted)
 template <int S>
 bool medium_maps(const rt_solver *s, bool unit_B, const phys::GroupTable &gt, double dx, double *map, double *hmap);

@@ -218,19 +218,20 @@ rt_status rtsn_detail::line_maps_s(rt_solver *s, bool unit_B, DeviceBuf &map_dev
 
 // A slab of regions: one map set per region, [region][2][WN][Lpad], each with its own group
 // table and dx; the reflective head cell is physical cell 0, so its map is region 0's.
+// unit_B: the maps of the material-coupled step (sources for B_g = 1) into map_unit, hmap_unit.
 template <int S>
-rt_status rtsn_detail::region_maps_s(rt_solver *s) {
+rt_status rtsn_detail::region_maps_s(rt_solver *s, bool unit_B) {
   constexpr int WN = map_count<S>();
   const size_t Lp = s->Lpad, R = s->regions.size();
   std::vector<double> hmap(WN * Lp, 0.0), map(R * 2 * WN * Lp, 0.0);
   for (size_t k = 0; k < R; ++k)
-    if (!medium_maps<S>(s, false, s->regions[k].gt, s->regions[k].dx, map.data() + k * 2 * WN * Lp,
+    if (!medium_maps<S>(s, unit_B, s->regions[k].gt, s->regions[k].dx, map.data() + k * 2 * WN * Lp,
                         k == 0 ? hmap.data() : nullptr))
       return fail(s, RT_ERR_PARAM, "cell map: a structurally zero coefficient is not zero (or a head-cell row differs from its line map)");
-  s->map_host.assign(map.begin(), map.begin() + 2 * WN * Lp);
+  if (!unit_B) s->map_host.assign(map.begin(), map.begin() + 2 * WN * Lp);
   rt_status st;
-  if ((st = upload(s, s->hmap, hmap.data(), hmap.size() * sizeof(double)))) return st;
-  if ((st = upload(s, s->map, map.data(), map.size() * sizeof(double)))) return st;
+  if ((st = upload(s, unit_B ? s->hmap_unit : s->hmap, hmap.data(), hmap.size() * sizeof(double)))) return st;
+  if ((st = upload(s, unit_B ? s->map_unit : s->map, map.data(), map.size() * sizeof(double)))) return st;
   return RT_OK;
 }
 
@@ -238,7 +239,7 @@ template <int S>
 static rt_status setup_lines_s(rt_solver *s) {
   const size_t Lp = s->Lpad;
   rt_status st;
-  if ((st = regional(s) ? region_maps_s<S>(s) : line_maps_s<S>(s, false, s->map, s->hmap))) return st;
+  if ((st = regional(s) ? region_maps_s<S>(s, false) : line_maps_s<S>(s, false, s->map, s->hmap))) return st;
   std::vector<double> lineB(2 * Lp, 0.0);
   for (int half = 0; half < 2; ++half)
     for (int gl = 0; gl < s->Gl; ++gl)
@@ -408,3 +409,6 @@ rt_status rtsn_detail::segment_target(rt_solver *h, int *w_out) {
 template rt_status rtsn_detail::line_maps_s<SCHEME_BE>(rt_solver *, bool, DeviceBuf &, DeviceBuf &);
 template rt_status rtsn_detail::line_maps_s<SCHEME_CN>(rt_solver *, bool, DeviceBuf &, DeviceBuf &);
 template rt_status rtsn_detail::line_maps_s<SCHEME_BDF2>(rt_solver *, bool, DeviceBuf &, DeviceBuf &);
+template rt_status rtsn_detail::region_maps_s<SCHEME_BE>(rt_solver *, bool);
+template rt_status rtsn_detail::region_maps_s<SCHEME_CN>(rt_solver *, bool);
+template rt_status rtsn_detail::region_maps_s<SCHEME_BDF2>(rt_solver *, bool);

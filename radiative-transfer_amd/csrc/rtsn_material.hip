@@ -24,7 +24,8 @@ static rt_status material_planck(rt_solver *s) {
 
 // dt W sum_g rho kappa_g dB_g/dT(T_max) / rho_cv over all G groups (rt_material_stability): the
 // emission's stiffness at the hottest cell, 1 / (1 + number) the Fleck factor there
-static double material_stability_number(const rt_solver *s, double T_max) {
+// (gt, rho_cv: the handle's own medium, or one region's)
+static double material_stability_number(const rt_solver *s, const phys::GroupTable &gt, double rho_cv, double T_max) {
   const int G = s->p.G;
   std::vector<double> lo(s->gt.e_edge.begin(), s->gt.e_edge.begin() + G), hi(s->gt.e_edge.begin() + 1,
                                                                              s->gt.e_edge.begin() + G + 1);
@@ -33,8 +34,8 @@ static double material_stability_number(const rt_solver *s, double T_max) {
   phys::gauss_legendre(s->M_full, phys::kFourPi, mu.data(), wt.data());
   double W = 0.0, sum = 0.0;
   for (double w : wt) W += w;
-  for (int g = 0; g < G; ++g) sum += s->gt.rho[g] * s->gt.kappa[g] * dB[g] * phys::kBoltzmannJPK;
-  return s->p.dt * W * sum / s->rho_cv;
+  for (int g = 0; g < G; ++g) sum += gt.rho[g] * gt.kappa[g] * dB[g] * phys::kBoltzmannJPK;
+  return s->p.dt * W * sum / rho_cv;
 }
 
 extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
@@ -44,16 +45,133 @@ extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
   std::vector<double> T(s->p.N);
   HIP_TRY(s, hipMemcpyAsync(T.data(), s->Tcell.p, sizeof(double) * T.size(), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
+  if (regional(s)) {  // the stiffest region, each at its own hottest cell
+    double worst = 0.0;
+    for (size_t k = 0; k < s->regions.size(); ++k) {
+      double T_max = 0.0;
+      for (int c = s->first_cell[k]; c < s->first_cell[k + 1]; ++c)
+        if (std::isfinite(T[c])) T_max = std::max(T_max, T[c]);
+      worst = std::max(worst, material_stability_number(s, s->regions[k].gt, s->rho_cv_r[k], T_max));
+    }
+    *number = worst;
+    return RT_OK;
+  }
   double T_max = 0.0;
   for (double t : T)
     if (std::isfinite(t)) T_max = std::max(T_max, t);
-  *number = material_stability_number(s, T_max);
+  *number = material_stability_number(s, s->gt, s->rho_cv, T_max);
+  return RT_OK;
+}
+
+// The Planck kernels' arguments that do not depend on the medium, and the quadrature's weight sums.
+static void material_common(rt_solver *s) {
+  PlanckCells &pc = s->pc;
+  phys::PlanckIntegrator().nodes(pc.node, pc.weight);
+  pc.e_edge = static_cast<const double *>(s->edges.p);
+  pc.G = s->p.G;
+  pc.g_lo = s->g_lo;
+  pc.Gl = s->Gl;
+  pc.N = s->p.N;
+  pc.a_c = phys::rad_a_long() * phys::kLight;
+  pc.kcon = phys::kBoltzmannJPK;
+  pc.accuracy = std::numeric_limits<double>::epsilon();
+  pc.sigma = static_cast<const double *>(s->sigma.p);
+  pc.dTlast = static_cast<const double *>(s->dTlast.p);
+  pc.owed = static_cast<double *>(s->owed.p);
+  pc.dB = static_cast<double *>(s->dBcell.p);
+  pc.Beff = static_cast<double *>(s->Beff.p);
+  pc.bpart = static_cast<double *>(s->bpart.p);
+  pc.b_scale = s->d_lo == 0 ? 1.0 : 0.0;  // direction shards: every one holds all groups, count b once
+  pc.sigma_all = static_cast<const double *>(s->sigma_all.p);
+  pc.Bcell = static_cast<const double *>(s->Bcell.p);
+  s->wsum = 0.0;
+  for (double w : s->wt) s->wsum += w;
+  std::vector<double> mu_all(s->M_full), wt_all(s->M_full);
+  phys::gauss_legendre(s->M_full, phys::kFourPi, mu_all.data(), wt_all.data());
+  s->wsum_all = 0.0;
+  for (double w : wt_all) s->wsum_all += w;
+}
+
+// Coupling on a slab of regions: the coupled step is the REG && CB wavefront chain on unit-B
+// maps (one set per region), the material kernels take each cell's own sigma_g(x) and
+// rho_cv(x).  No segment buffers, fused sums or correction tables: phi comes from the moments
+// kernels after each step.
+extern "C" rt_status rt_material_enable_regions(rt_solver *s, const double *rho_cv, int nregions,
+                                                const double *T_cells) {
+  if (!s) return fail(nullptr, RT_ERR_ARG, "rt_material_enable_regions: NULL handle");
+  if (!rho_cv) return fail(s, RT_ERR_ARG, "rt_material_enable_regions: NULL rho_cv");
+  const int R = regional(s) ? static_cast<int>(s->regions.size()) : 1;
+  if (nregions != R)
+    return fail(s, RT_ERR_ARG, "rt_material_enable_regions: nregions must be the handle's " + std::to_string(R));
+  for (int k = 0; k < R; ++k)
+    if (!(rho_cv[k] > 0.0) || !std::isfinite(rho_cv[k]))
+      return fail(s, RT_ERR_ARG, "rt_material_enable_regions: every rho_cv must be > 0");
+  if (!regional(s)) return rt_material_enable(s, rho_cv[0], T_cells);
+  if (s->p.use_correction && s->p.V != 0.0)
+    return fail(s, RT_ERR_PARAM, "material coupling needs the v/c correction off (V = 0 or use_correction = 0)");
+  HIP_TRY(s, hipSetDevice(s->device));
+  rt_status st = finalize(s);  // queued steps run on the uncoupled plan's chain first
+  if (st) return st;
+  const size_t N = s->p.N, NG = N * s->Gl, G = s->p.G;
+  if (!s->Tcell.p) {
+    hipError_t e = dalloc(s->Tcell, sizeof(double) * N);
+    if (!e) e = dalloc(s->Bcell, sizeof(double) * NG);
+    if (!e) e = dalloc(s->Beff, sizeof(double) * NG);
+    if (!e) e = dalloc(s->owed, sizeof(double) * NG);
+    if (!e) e = dalloc(s->dBcell, sizeof(double) * NG);
+    if (!e) e = dalloc(s->dTlast, sizeof(double) * N);
+    if (!e) e = dalloc(s->bpart, sizeof(double) * N);
+    if (!e) e = dalloc(s->qbuf, sizeof(double) * 2 * N);
+    if (!e) e = dalloc(s->edges, sizeof(double) * (G + 1));
+    if (!e) e = dalloc(s->rmaterial, sizeof(double) * (R + R * G));
+    if (!e) e = dalloc(s->map_unit, s->map.bytes);
+    if (!e) e = dalloc(s->hmap_unit, s->hmap.bytes);
+    if (e) return fail(s, RT_ERR_NOMEM, std::string("material buffers: ") + hipGetErrorString(e));
+  }
+  s->phi_fused = false;  // a line's directions sit in different workgroups
+  switch (s->scheme) {
+    case SCHEME_BE: st = region_maps_s<SCHEME_BE>(s, true); break;
+    case SCHEME_CN: st = region_maps_s<SCHEME_CN>(s, true); break;
+    default: st = region_maps_s<SCHEME_BDF2>(s, true); break;
+  }
+  if (st) return st;
+  std::vector<double> T0(N);
+  for (int k = 0; k < R; ++k)
+    std::fill(T0.begin() + s->first_cell[k], T0.begin() + s->first_cell[k + 1], s->regions[k].p.T);
+  if (T_cells) std::copy(T_cells, T_cells + N, T0.begin());
+  if ((st = upload(s, s->Tcell, T0.data(), N * sizeof(double)))) return st;
+  HIP_TRY(s, hipMemsetAsync(s->dTlast.p, 0, sizeof(double) * N, s->stream));  // nothing owed yet
+  HIP_TRY(s, hipMemsetAsync(s->owed.p, 0, sizeof(double) * NG, s->stream));
+  HIP_TRY(s, hipMemsetAsync(s->dBcell.p, 0, sizeof(double) * NG, s->stream));
+  if ((st = upload(s, s->edges, s->gt.e_edge.data(), (G + 1) * sizeof(double)))) return st;
+  {
+    std::vector<double> rm(R + R * G);
+    for (int k = 0; k < R; ++k) {
+      rm[k] = rho_cv[k];
+      for (size_t g = 0; g < G; ++g) rm[R + k * G + g] = s->regions[k].gt.rho[g] * s->regions[k].gt.kappa[g];
+    }
+    if ((st = upload(s, s->rmaterial, rm.data(), rm.size() * sizeof(double)))) return st;
+  }
+  material_common(s);
+  PlanckCells &pc = s->pc;
+  pc.sigma_all = nullptr;  // (every cell reads its region's row)
+  pc.cell_region = static_cast<const int *>(s->cell_region.p);
+  pc.rsigma = static_cast<const double *>(s->rmedium.p);  // its first [regions][Gl] doubles: rho kappa
+  pc.rho_cv_r = static_cast<const double *>(s->rmaterial.p);
+  pc.rsigma_all = pc.rho_cv_r + R;
+  s->rho_cv_r.assign(rho_cv, rho_cv + R);
+  s->rho_cv = rho_cv[0];
+  if ((st = material_planck(s))) return st;
+  HIP_TRY(s, hipStreamSynchronize(s->stream));  // T0 dies at return
+  s->material = true;  // from here the chain is the one-step plan's (region_wave_plan)
   return RT_OK;
 }
 
 extern "C" rt_status rt_material_enable(rt_solver *s, double rho_cv, const double *T_cells) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_material_enable: NULL handle");
-  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_material_enable: no material coupling on a region handle");
+  if (regional(s))
+    return fail(s, RT_ERR_STATE, "rt_material_enable: a region handle takes rt_material_enable_regions (one rho_cv "
+                                 "per region)");
   if (!(rho_cv > 0.0) || !std::isfinite(rho_cv)) return fail(s, RT_ERR_ARG, "rt_material_enable: rho_cv must be > 0");
   if (s->p.use_correction && s->p.V != 0.0)
     return fail(s, RT_ERR_PARAM, "material coupling needs the v/c correction off (V = 0 or use_correction = 0)");
@@ -115,33 +233,7 @@ extern "C" rt_status rt_material_enable(rt_solver *s, double rho_cv, const doubl
     for (int g = 0; g < s->p.G; ++g) sig[g] = s->gt.rho[g] * s->gt.kappa[g];
     if ((st = upload(s, s->sigma_all, sig.data(), sig.size() * sizeof(double)))) return st;
   }
-  PlanckCells &pc = s->pc;
-  phys::PlanckIntegrator().nodes(pc.node, pc.weight);
-  pc.e_edge = static_cast<const double *>(s->edges.p);
-  pc.G = s->p.G;
-  pc.g_lo = s->g_lo;
-  pc.Gl = s->Gl;
-  pc.N = s->p.N;
-  pc.a_c = phys::rad_a_long() * phys::kLight;
-  pc.kcon = phys::kBoltzmannJPK;
-  pc.accuracy = std::numeric_limits<double>::epsilon();
-  pc.sigma = static_cast<const double *>(s->sigma.p);
-  pc.dTlast = static_cast<const double *>(s->dTlast.p);
-  pc.owed = static_cast<double *>(s->owed.p);
-  pc.dB = static_cast<double *>(s->dBcell.p);
-  pc.Beff = static_cast<double *>(s->Beff.p);
-  pc.bpart = static_cast<double *>(s->bpart.p);
-  pc.b_scale = s->d_lo == 0 ? 1.0 : 0.0;  // direction shards: every one holds all groups, count b once
-  pc.sigma_all = static_cast<const double *>(s->sigma_all.p);
-  pc.Bcell = static_cast<const double *>(s->Bcell.p);
-  s->wsum = 0.0;
-  for (double w : s->wt) s->wsum += w;
-  {
-    std::vector<double> mu_all(s->M_full), wt_all(s->M_full);
-    phys::gauss_legendre(s->M_full, phys::kFourPi, mu_all.data(), wt_all.data());
-    s->wsum_all = 0.0;
-    for (double w : wt_all) s->wsum_all += w;
-  }
+  material_common(s);
   s->rho_cv = rho_cv;
   if ((st = material_planck(s))) return st;
   HIP_TRY(s, hipStreamSynchronize(s->stream));  // T0 dies at return
@@ -159,6 +251,14 @@ extern "C" rt_status rt_material_sweep(rt_solver *s, double *d_q) {
   double *q = d_q ? d_q : static_cast<double *>(s->qbuf.p);
   const double *B = static_cast<const double *>(s->Bcell.p), *sig = static_cast<const double *>(s->sigma.p);
   const double *bp = static_cast<const double *>(s->bpart.p);
+  if (regional(s)) {  // one launch of the coupled chain, then phi by the moments kernels
+    if ((st = finalize(s))) return st;
+    if ((st = wave_coupled_pass(s))) return st;
+    if ((st = compute_moments(s))) return st;
+    HIP_TRY(s, launch_material_q(static_cast<const double *>(s->mom.p), 1, B, static_cast<const double *>(s->rmedium.p),
+                                 s->wsum, bp, q, s->Gl, s->p.N, s->stream, static_cast<const int *>(s->cell_region.p)));
+    return RT_OK;
+  }
   if (s->phi_fused) {
     // one pass over the state: the pass sums w psi of its provisional cells, the
     // correction kernel adds the cross-segment correction's share (no state
@@ -272,9 +372,12 @@ extern "C" rt_status rt_get_material_transit(rt_solver *s, double *E) {
   HIP_TRY(s, hipSetDevice(s->device));
   DeviceBuf d;
   HIP_TRY(s, dalloc(d, sizeof(double) * s->p.N));
-  hipError_t e = launch_material_transit(static_cast<const double *>(s->Bcell.p), static_cast<const double *>(s->Beff.p),
-                                         static_cast<const double *>(s->owed.p), static_cast<const double *>(s->sigma.p),
-                                         s->p.dt * s->wsum, static_cast<double *>(d.p), s->Gl, s->p.N, s->stream);
+  // (a region handle: each cell's own sigma_g(x), rmedium's first [regions][Gl] doubles)
+  hipError_t e = launch_material_transit(
+      static_cast<const double *>(s->Bcell.p), static_cast<const double *>(s->Beff.p),
+      static_cast<const double *>(s->owed.p), static_cast<const double *>(regional(s) ? s->rmedium.p : s->sigma.p),
+      s->p.dt * s->wsum, static_cast<double *>(d.p), s->Gl, s->p.N, s->stream,
+      regional(s) ? static_cast<const int *>(s->cell_region.p) : nullptr);
   if (e == hipSuccess) e = hipMemcpyAsync(E, d.p, sizeof(double) * s->p.N, hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   (void)hipStreamSynchronize(s->stream);

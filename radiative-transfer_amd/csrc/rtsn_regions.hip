@@ -35,7 +35,9 @@ rt_status rtsn_detail::setup_regions(rt_solver *s, const rt_region *r, int nregi
 }
 
 WavePlan rtsn_detail::region_wave_plan(const rt_solver *s, int wave_max) {
-  const regions::Plan p = regions::plan(s->first_cell, s->p.bc_left_indicator == 2, wave_max, s->wave_cells);
+  // a coupled handle only ever launches one step: the chain is planned for that (regions.hpp)
+  const regions::Plan p = regions::plan(s->first_cell, s->p.bc_left_indicator == 2, wave_max, s->wave_cells,
+                                        s->material ? 1 : 1000);
   return WavePlan{p.C, p.waves, p.lanes};
 }
 

@@ -455,6 +455,36 @@ rt_status rtsn_detail::wave_flush(rt_solver *s) {
   return RT_OK;
 }
 
+// The material-coupled step of a region handle: one launch of the REG && CB chain (the unit-B
+// maps, one set per region, their constants scaled by each cell's emission Beff), one step --
+// the stored state read once and written once; the caller has finalized (nothing queued).
+rt_status rtsn_detail::wave_coupled_pass(rt_solver *s) {
+  const WavePlan wp = wave_plan(s);
+  int ci = 0;
+  while (ci < 3 && (1 << ci) != wp.C) ++ci;
+  if (!wp.C || s->lane_off[ci] < 0) return fail(s, RT_ERR_STATE, "regions: no admissible chain");
+  SegArgs a = seg_args(s);
+  a.Gl = s->Gl;
+  a.H = s->H;
+  a.lane_region = static_cast<const int *>(s->lane_region.p) + s->lane_off[ci];
+  a.map = static_cast<const double *>(s->map_unit.p);
+  a.hmap = static_cast<const double *>(s->hmap_unit.p);
+  a.bcell = static_cast<const double *>(s->Beff.p);  // the step's linearised emission
+  hipEvent_t e1;
+  rt_status st = event_begin(s, &e1);
+  if (st) return st;
+  const hipError_t e = launch_wavefront(s->scheme, wp, a, 1, s->stream);
+  if (e != hipSuccess) {
+    event_abort(s, e1);
+    return fail(s, RT_ERR_DEVICE, std::string("coupled wavefront launch: ") + hipGetErrorString(e));
+  }
+  if ((st = event_end(s, e1))) return st;
+  ++s->state_version;
+  for (long long &t : s->tau) ++t;
+  ++s->target;
+  return RT_OK;
+}
+
 static rt_status wave_advance(rt_solver *s, int nsteps) {
   if (!s->wqueued)
     if (rt_status st = finalize(s)) return st;  // the stored state exact at the requested time

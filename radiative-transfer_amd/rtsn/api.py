@@ -95,6 +95,7 @@ def lib():
                                                 C.POINTER(vp)]
         rp = C.POINTER(rt_region)
         L.rt_regions_plan.argtypes = [rp, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
+        L.rt_regions_plan_steps.argtypes = [rp, C.c_int, C.c_int, C.c_int, C.c_longlong] + [C.POINTER(C.c_int)] * 3
         L.rt_regions_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(rp), C.POINTER(C.c_int)]
         L.rt_regions_free.argtypes = [rp]
         L.rt_regions_free.restype = None
@@ -146,6 +147,7 @@ def lib():
         L.rt_get_wavefront_waves.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.rt_set_wavefront_cells.argtypes = [vp, C.c_int]
         L.rt_material_enable.argtypes = [vp, C.c_double, dp]
+        L.rt_material_enable_regions.argtypes = [vp, dp, C.c_int, dp]
         L.rt_material_sweep.argtypes = [vp, vp]
         L.rt_material_update.argtypes = [vp, vp]
         L.rt_material_step.argtypes = [vp, C.c_int]
@@ -251,14 +253,15 @@ def _region_structs(regions, G: int, keep: list):
     return arr
 
 
-def regions_plan(regions, reflective: bool = False, max_waves: int = 8) -> dict:
-    """rt_regions_plan (host only): the wavefront chain a slab of regions takes --
+def regions_plan(regions, reflective: bool = False, max_waves: int = 8, nsteps: int = 1000) -> dict:
+    """rt_regions_plan_steps (host only): the wavefront chain a slab of regions takes for
+    launches of nsteps steps (1000: rt_regions_plan's rule; 1: a material-coupled handle's) --
     {"cells_per_lane", "waves", "lanes"}; RtError status 3 when no admissible chain fits."""
     keep: list = []
     arr = _region_structs([dict(r, group_kappa=None) for r in regions], 0, keep)
     c, w, n = C.c_int(), C.c_int(), C.c_int()
-    _check(lib().rt_regions_plan(arr, len(regions), int(bool(reflective)), int(max_waves), C.byref(c), C.byref(w),
-                                 C.byref(n)), "rt_regions_plan")
+    _check(lib().rt_regions_plan_steps(arr, len(regions), int(bool(reflective)), int(max_waves), int(nsteps),
+                                       C.byref(c), C.byref(w), C.byref(n)), "rt_regions_plan_steps")
     return {"cells_per_lane": c.value, "waves": w.value, "lanes": n.value}
 
 
@@ -570,6 +573,18 @@ class Solver:
             raise ValueError("material_enable: T_cells must hold N values")
         _check(lib().rt_material_enable(self._h, float(rho_cv), None if T is None else _dp(T)),
                "rt_material_enable", self._h)
+        return self.material_stability()
+
+    def material_enable_regions(self, rho_cv, T_cells=None):
+        """T(x) coupling on a region handle (rt_material_enable_regions): rho_cv a sequence, one
+        heat capacity > 0 per region; T_cells (N) or None for every cell at its region's T.
+        Returns the stability number (the stiffest region's)."""
+        rc = np.ascontiguousarray(rho_cv, dtype=np.float64).ravel()
+        T = None if T_cells is None else np.ascontiguousarray(T_cells, dtype=np.float64)
+        if T is not None and T.size != self.N:
+            raise ValueError("material_enable_regions: T_cells must hold N values")
+        _check(lib().rt_material_enable_regions(self._h, _dp(rc), int(rc.size), None if T is None else _dp(T)),
+               "rt_material_enable_regions", self._h)
         return self.material_stability()
 
     def material_stability(self) -> float:
