@@ -159,12 +159,13 @@ class RegionReference:
     """oracle/fused_np.py's FusedSolver with a LineSet per region: sweep_step's loop with the
     cell's own LineSet, mirrored for the mu < 0 half (upwind cell k is physical cell N-1-k)."""
 
-    def __init__(self, oracle_mod, p, regions):
+    def __init__(self, oracle_mod, p, regions, g_lo=LO, g_hi=HI):
         import fused_np
         self.fn = fused_np
         self.p = p
         M, N = p["M"], p["N"]
-        self.M, self.N, self.G = M, N, HI - LO
+        self.M, self.N, self.G = M, N, g_hi - g_lo
+        sl = slice(g_lo, g_hi)
         h = M // 2
         self.cell_region = np.repeat(np.arange(len(regions)), [r["cells"] for r in regions])
         assert self.cell_region.size == N
@@ -173,15 +174,16 @@ class RegionReference:
         self.tables = []
         for r in regions:
             pr = dict(p, rho=r["rho"], kappa_grey=r["kappa_grey"], T=r["T"], group_kappa=r["group_kappa"],
+                      have_group_kappa=int(r["group_kappa"] is not None),  # None: the region's kappa_grey
                       N=r["cells"], X=r["width"], dx=r["width"] / r["cells"])
-            o = oracle_mod.OracleSolver(pr, g_lo=LO, g_hi=HI)
+            o = oracle_mod.OracleSolver(pr, g_lo=g_lo, g_hi=g_hi)
             g, c = o.groups(), o.correction_coeffs()
             self.mu, self.wt = o.quad()
             # the solver-owned table (zero unless a boundary is "source"); no medium enters it
-            self.psi_source = o.psi_source()[:, LO:HI]
-            self.tables.append(dict(B=g["B"][LO:HI], kappa=g["kappa"][LO:HI], sigma=r["rho"] * g["kappa"][LO:HI],
-                                    dBdT=g["dBdT"][LO:HI], de_ave=g["de_ave"][LO:HI],
-                                    cor=[c[k][LO:HI] for k in ("cor1", "cor2", "cor3")]))
+            self.psi_source = o.psi_source()[:, sl]
+            self.tables.append(dict(B=g["B"][sl], kappa=g["kappa"][sl], sigma=r["rho"] * g["kappa"][sl],
+                                    dBdT=g["dBdT"][sl], de_ave=g["de_ave"][sl],
+                                    cor=[c[k][sl] for k in ("cor1", "cor2", "cor3")]))
         self.idx, self.lines, self.E = {}, {}, {}
         for half in (0, 1):
             I = np.tile([(h - 1 - ip) if half == 0 else (h + ip) for ip in range(h)], self.G)

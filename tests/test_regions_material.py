@@ -28,10 +28,10 @@ def uniform_regions(p, cells):
                  group_kappa=p["group_kappa"]) for c in cells]
 
 
-def _pin(oracle_mod, p, rho_cv, T0, steps):
+def _pin(oracle_mod, p, rho_cv, T0, steps, cuts=CUTS):
     orc = oracle_mod.OracleSolver(p)
     orc.material_enable(rho_cv, T0)
-    ref = RegionMaterialReference(oracle_mod, p, uniform_regions(p, CUTS), [rho_cv] * len(CUTS), T0)
+    ref = RegionMaterialReference(oracle_mod, p, uniform_regions(p, cuts), [rho_cv] * len(cuts), T0)
     np.testing.assert_array_equal(ref.ends(), orc.ends())  # psi = B_g at the start, both
     for _ in range(steps):
         orc.material_step(1)
