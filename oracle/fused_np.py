@@ -29,48 +29,53 @@ C_LIGHT = 299.79245800
 class LineSet:
     """Per-line constants of the lines of one half (mu < 0 or mu > 0)."""
 
-    def __init__(self, mu_signed, sigma, Bg, cor1, cor2, cor3, V, dx, dt, ts_method, use_correction):
-        self.mu = np.asarray(mu_signed, dtype=np.float64)
+    def __init__(self, mu_signed, sigma, Bg, cor1, cor2, cor3, V, dx, dt, ts_method, use_correction,
+                 dtype=np.float64):
+        # dtype: the arithmetic's format.  The inputs are the fp64 tables and parameters, cast
+        # exactly; with np.longdouble every constant below is formed in extended precision.
+        f = self.dtype = np.dtype(dtype).type
+        self.mu = np.asarray(mu_signed, dtype=f)
         self.m = np.abs(self.mu)
-        self.sigma = np.asarray(sigma, dtype=np.float64)   # rho*kappa
-        self.B = np.asarray(Bg, dtype=np.float64)
-        self.dx = dx
-        self.dt = dt
+        self.sigma = np.asarray(sigma, dtype=f)   # rho*kappa
+        self.B = np.asarray(Bg, dtype=f)
+        dx = self.dx = f(dx)
+        dt = self.dt = f(dt)
         self.ts = ts_method
-        tau = dt / 2.0 if ts_method == 3 else dt
+        tau = dt / f(2.0) if ts_method == 3 else dt
         self.tau = tau
-        c = C_LIGHT
+        c = f(C_LIGHT)
         # emission + correction source S = Sc + Sl * (e_in + e_out) (psi = mean of the nodes)
-        half = 0.5 * c * tau * dx
+        half = f(0.5) * c * tau * dx
         self.Sc = half * self.sigma * self.B
         if use_correction:
-            beta = V / c
-            self.Sc = self.Sc + half * ((np.asarray(cor2) * self.mu) * beta - np.asarray(cor3) * self.mu ** 2 * beta ** 2)
-            self.Sl = half * np.asarray(cor1) * self.mu * beta * 0.5
+            beta = f(V) / c
+            cor1, cor2, cor3 = (np.asarray(a, dtype=f) for a in (cor1, cor2, cor3))
+            self.Sc = self.Sc + half * ((cor2 * self.mu) * beta - cor3 * self.mu ** 2 * beta ** 2)
+            self.Sl = half * cor1 * self.mu * beta * f(0.5)
         else:
             self.Sl = np.zeros_like(self.m)
-        hd = 0.5 * dx
+        hd = f(0.5) * dx
         self.hd = hd
         # BE(tau)  (solver.cpp:319-404)
-        a = 1.0 + c * tau * self.sigma
+        a = f(1.0) + c * tau * self.sigma
         b = c * tau * self.m
-        d = (a * dx + b) / 2.0
-        self.be = dict(b=b, inv=self._inv(d, b / 2.0))
+        d = (a * dx + b) / f(2.0)
+        self.be = dict(b=b, inv=self._inv(d, b / f(2.0)))
         # CN(tau)  (solver.cpp:407-490)
-        t = 0.5 * c * tau * self.sigma
-        A = 0.5 * c * self.m * tau
-        Bp, Cp = 1.0 + t, 1.0 - t
-        d = 0.5 * (A + Bp * dx)
-        self.cn = dict(A=A, k1=0.5 * (Cp * dx - A), k2=0.5 * A, inv=self._inv(d, A / 2.0))
+        t = f(0.5) * c * tau * self.sigma
+        A = f(0.5) * c * self.m * tau
+        Bp, Cp = f(1.0) + t, f(1.0) - t
+        d = f(0.5) * (A + Bp * dx)
+        self.cn = dict(A=A, k1=f(0.5) * (Cp * dx - A), k2=f(0.5) * A, inv=self._inv(d, A / f(2.0)))
         # BDF(tau, const_B with the full dt)  (solver.cpp:493-587)
-        t = c * self.sigma * tau / 6.0
-        Ab = 1.0 + t
-        Bc = c * self.m * dt / 6.0
-        Cb = 1.0 - 4.0 * t
+        t = c * self.sigma * tau / f(6.0)
+        Ab = f(1.0) + t
+        Bc = c * self.m * dt / f(6.0)
+        Cb = f(1.0) - f(4.0) * t
         D = t
-        d = 0.5 * (Ab * dx + Bc)
-        self.bdf = dict(Bc=Bc, q1=0.5 * (Cb * dx - 4.0 * Bc), q2=2.0 * Bc, q3=0.5 * (Bc + D * dx), q4=0.5 * Bc,
-                        inv=self._inv(d, 0.5 * Bc))
+        d = f(0.5) * (Ab * dx + Bc)
+        self.bdf = dict(Bc=Bc, q1=f(0.5) * (Cb * dx - f(4.0) * Bc), q2=f(2.0) * Bc, q3=f(0.5) * (Bc + D * dx),
+                        q4=f(0.5) * Bc, inv=self._inv(d, f(0.5) * Bc))
 
     @staticmethod
     def _inv(d, o):
@@ -105,13 +110,16 @@ class LineSet:
         return i00 * r_in + i01 * r_out, i10 * r_in + i11 * r_out
 
 
-def sweep_step(ls: LineSet, E: np.ndarray, bdry: np.ndarray, negative_half: bool) -> np.ndarray:
+def sweep_step(ls: LineSet, E: np.ndarray, bdry: np.ndarray, negative_half: bool, dtype=np.float64) -> np.ndarray:
     """One full step (1 substep for BE/CN, the 4 fused substeps for BDF2) of
     the lines in `ls`, state E (lines, N, 2) in the upwind frame, updated in
     place.  bdry (nsub, lines) are the per-substep inflow values.  Returns the
     per-substep outflow scalars (nsub, lines) = the carried values after the
-    last cell (what reflective partners read, solver.cpp:677-684)."""
+    last cell (what reflective partners read, solver.cpp:677-684).  dtype: the format of ls,
+    E and the result (bdry is cast to it exactly)."""
     L, N, _ = E.shape
+    assert E.dtype == np.dtype(dtype) and ls.dtype is np.dtype(dtype).type
+    bdry = np.asarray(bdry, dtype=dtype)
     if ls.ts == 1:
         x = bdry[0].copy()
         for k in range(N):
@@ -153,11 +161,14 @@ def sweep_step(ls: LineSet, E: np.ndarray, bdry: np.ndarray, negative_half: bool
 class FusedSolver:
     """Whole-run driver over the reference's configuration dict (oracle.parse_prm)."""
 
-    def __init__(self, params: dict, mu, B, kappa, cor1, cor2, cor3, psi_source):
+    def __init__(self, params: dict, mu, B, kappa, cor1, cor2, cor3, psi_source, dtype=np.float64):
+        """dtype np.longdouble: mu, B, kappa, cor1..3, psi_source and the parameters (fp64) are
+        cast exactly and every operation runs in extended precision."""
         self.p = params
+        f = self.dtype = np.dtype(dtype).type
         M, G, N = params["M"], params["G"], params["N"]
         self.M, self.G, self.N = M, G, N
-        self.mu = np.asarray(mu)
+        self.mu = np.asarray(mu, dtype=f)
         h = M // 2
         # line l = i' + h*g within a half; i' counts |mu| upwards from the centre
         self.idx = {}
@@ -166,7 +177,7 @@ class FusedSolver:
             I = np.array([[i for i in ii] for _ in range(G)]).ravel()          # (G*h,) direction
             Gi = np.repeat(np.arange(G), h)                                    # group
             self.idx[half] = (I, Gi)
-        sigma = params["rho"] * np.asarray(kappa)
+        sigma = f(params["rho"]) * np.asarray(kappa, dtype=f)
         ts = params["ts_method"]
         self.nsub = 4 if ts == 3 else 1
         self.lines = {}
@@ -175,9 +186,21 @@ class FusedSolver:
             I, Gi = self.idx[half]
             self.lines[half] = LineSet(self.mu[I], sigma[Gi], np.asarray(B)[Gi], np.asarray(cor1)[Gi],
                                        np.asarray(cor2)[Gi], np.asarray(cor3)[Gi], params["V"], params["dx"],
-                                       params["dt"], ts, bool(params["use_correction"]))
-            self.E[half] = np.repeat(np.asarray(B)[Gi][:, None, None], N, axis=1).repeat(2, axis=2).astype(np.float64)
-        self.psi_source = np.asarray(psi_source)  # (M, G)
+                                       params["dt"], ts, bool(params["use_correction"]), dtype=f)
+            self.E[half] = np.repeat(np.asarray(B)[Gi][:, None, None], N, axis=1).repeat(2, axis=2).astype(f)
+        self.psi_source = np.asarray(psi_source, dtype=f)  # (M, G)
+
+    def set_ends(self, ends):
+        """The node array (M, G, N, 2) in the reference's physical frame, cast exactly."""
+        ends = np.asarray(ends, dtype=self.dtype)
+        for half in (0, 1):
+            I, Gi = self.idx[half]
+            if half == 0:
+                self.E[0][:, :, 0] = ends[I, Gi, ::-1, 1]
+                self.E[0][:, :, 1] = ends[I, Gi, ::-1, 0]
+            else:
+                self.E[1][:, :, 0] = ends[I, Gi, :, 0]
+                self.E[1][:, :, 1] = ends[I, Gi, :, 1]
 
     def step(self):
         p = self.p
@@ -187,20 +210,20 @@ class FusedSolver:
         if p["bc_right"] == 1:
             b = self.psi_source[I, Gi]
         else:
-            b = np.zeros(len(I))
-        out_neg = sweep_step(self.lines[0], self.E[0], np.repeat(b[None], nsub, axis=0), True)
+            b = np.zeros(len(I), dtype=self.dtype)
+        out_neg = sweep_step(self.lines[0], self.E[0], np.repeat(b[None], nsub, axis=0), True, self.dtype)
         # mu > 0 lines: left boundary (solver.cpp:665-692; 0 falls through to source)
         I, Gi = self.idx[1]
         if p["bc_left"] == 2:
             bd = out_neg  # same (i', g) ordering in both halves
         else:
             bd = np.repeat(self.psi_source[I, Gi][None], nsub, axis=0)
-        sweep_step(self.lines[1], self.E[1], bd, False)
+        sweep_step(self.lines[1], self.E[1], bd, False, self.dtype)
 
     def ends(self) -> np.ndarray:
         """(M, G, N, 2) in the reference's physical frame."""
         M, G, N = self.M, self.G, self.N
-        out = np.empty((M, G, N, 2))
+        out = np.empty((M, G, N, 2), dtype=self.dtype)
         for half in (0, 1):
             I, Gi = self.idx[half]
             E = self.E[half]

@@ -48,42 +48,51 @@ template <> struct SchemeDim<SCHEME_BE> { static constexpr int K = 1; };
 template <> struct SchemeDim<SCHEME_CN> { static constexpr int K = 2; };
 template <> struct SchemeDim<SCHEME_BDF2> { static constexpr int K = 5; };
 
-struct LineConst {
-  double c[LC_COUNT];
+// R: the format of the algebra.  The kernels never run it (they apply the map below); the
+// host derives each line's map from it in long double and rounds the coefficients once, so a
+// coefficient that cancels (c dt / dx >> 1: k1 = (Cp dx - A) / 2 against A) keeps its digits.
+template <class R>
+struct LineConstT {
+  R c[LC_COUNT];
 };
+using LineConst = LineConstT<double>;
 
-__host__ __device__ __forceinline__ double src(const LineConst &L, double ein, double eout) {
+template <class R>
+__host__ __device__ __forceinline__ R src(const LineConstT<R> &L, R ein, R eout) {
   return L.c[LC_SC] + L.c[LC_SL] * (ein + eout);
 }
 
 // Backward Euler cell (solver.cpp:319-404)
-__host__ __device__ __forceinline__ void cell_be(const LineConst &L, double hd, double ein, double eout, double x,
-                                                 double &uin, double &uout) {
-  const double S = src(L, ein, eout);
-  const double rin = S + L.c[LC_BE_B] * x + hd * ein;
-  const double rout = S + hd * eout;
+template <class R>
+__host__ __device__ __forceinline__ void cell_be(const LineConstT<R> &L, R hd, R ein, R eout, R x,
+                                                 R &uin, R &uout) {
+  const R S = src(L, ein, eout);
+  const R rin = S + L.c[LC_BE_B] * x + hd * ein;
+  const R rout = S + hd * eout;
   uin = L.c[LC_BE_I0] * rin - L.c[LC_BE_I1] * rout;
   uout = L.c[LC_BE_I1] * rin + L.c[LC_BE_I0] * rout;
 }
 
 // Crank-Nicolson cell (solver.cpp:407-490): xp = prev_ends of the upwind cell, xh = half_local_bdry
-__host__ __device__ __forceinline__ void cell_cn(const LineConst &L, double hd, double ein, double eout, double xp,
-                                                 double xh, double &uin, double &uout) {
-  const double S = src(L, ein, eout);
-  const double rin = S + L.c[LC_CN_K1] * ein - L.c[LC_CN_K2] * eout + L.c[LC_CN_A] * (xp + xh);
-  const double rout = S + L.c[LC_CN_K2] * ein + L.c[LC_CN_K1] * eout;
+template <class R>
+__host__ __device__ __forceinline__ void cell_cn(const LineConstT<R> &L, R hd, R ein, R eout, R xp,
+                                                 R xh, R &uin, R &uout) {
+  const R S = src(L, ein, eout);
+  const R rin = S + L.c[LC_CN_K1] * ein - L.c[LC_CN_K2] * eout + L.c[LC_CN_A] * (xp + xh);
+  const R rout = S + L.c[LC_CN_K2] * ein + L.c[LC_CN_K1] * eout;
   uin = L.c[LC_CN_I0] * rin - L.c[LC_CN_I1] * rout;
   uout = L.c[LC_CN_I1] * rin + L.c[LC_CN_I0] * rout;
 }
 
 // BDF corrector cell (solver.cpp:493-587); (ein, eout) = state at substep start (source only)
-__host__ __device__ __forceinline__ void cell_bdf(const LineConst &L, double ein, double eout, double hin,
-                                                  double hout, double pin, double pout, double x, double xh,
-                                                  double xp, double &uin, double &uout) {
-  const double S = src(L, ein, eout);
-  const double rin = S + L.c[LC_BD_Q1] * hin - L.c[LC_BD_Q2] * hout - L.c[LC_BD_Q3] * pin - L.c[LC_BD_Q4] * pout +
-                     L.c[LC_BD_BC] * (x + 4.0 * xh + xp);
-  const double rout = S + L.c[LC_BD_Q2] * hin + L.c[LC_BD_Q1] * hout + L.c[LC_BD_Q4] * pin - L.c[LC_BD_Q3] * pout;
+template <class R>
+__host__ __device__ __forceinline__ void cell_bdf(const LineConstT<R> &L, R ein, R eout, R hin,
+                                                  R hout, R pin, R pout, R x, R xh,
+                                                  R xp, R &uin, R &uout) {
+  const R S = src(L, ein, eout);
+  const R rin = S + L.c[LC_BD_Q1] * hin - L.c[LC_BD_Q2] * hout - L.c[LC_BD_Q3] * pin - L.c[LC_BD_Q4] * pout +
+                     L.c[LC_BD_BC] * (x + R(4.0) * xh + xp);
+  const R rout = S + L.c[LC_BD_Q2] * hin + L.c[LC_BD_Q1] * hout + L.c[LC_BD_Q4] * pin - L.c[LC_BD_Q3] * pout;
   uin = L.c[LC_BD_I0] * rin - L.c[LC_BD_I1] * rout;
   uout = L.c[LC_BD_I1] * rin + L.c[LC_BD_I0] * rout;
 }
@@ -91,24 +100,25 @@ __host__ __device__ __forceinline__ void cell_bdf(const LineConst &L, double ein
 // One BDF2 full step of one cell with explicit upwind inputs.
 // x0/xh/x2/x3: the substeps' carried scalars; xp1/xp3: prev-state upwind node
 // seen by CN / BDF; hup: half-state upwind node seen by BDF.
-__host__ __device__ __forceinline__ void cell_bdf2_explicit(const LineConst &L, double hd, bool neg, double pin,
-                                                            double pout, double x0, double xh, double x2, double x3,
-                                                            double xp1, double xp3, double hup, double &e1out,
-                                                            double &e2out, double &e3out, double &oin,
-                                                            double &oout) {
-  double e1in, e2in, e3in;
+template <class R>
+__host__ __device__ __forceinline__ void cell_bdf2_explicit(const LineConstT<R> &L, R hd, bool neg, R pin,
+                                                            R pout, R x0, R xh, R x2, R x3,
+                                                            R xp1, R xp3, R hup, R &e1out,
+                                                            R &e2out, R &e3out, R &oin,
+                                                            R &oout) {
+  R e1in, e2in, e3in;
   cell_be(L, hd, pin, pout, x0, e1in, e1out);                    // substep 0: BE predictor
   cell_cn(L, hd, e1in, e1out, xp1, xh, e2in, e2out);             // substep 1: CN corrector
-  const double hin = neg ? e2in : e1in, hout = neg ? e2out : e1out;  // half_ends (:733)
+  const R hin = neg ? e2in : e1in, hout = neg ? e2out : e1out;  // half_ends (:733)
   cell_be(L, hd, e2in, e2out, x2, e3in, e3out);                  // substep 2: BE predictor
   cell_bdf(L, e3in, e3out, hin, hout, pin, pout, x3, hup, xp3, oin, oout);  // substep 3: BDF
 }
 
 // Generic interior cell: X -> X' for scheme S; (pin, pout) = step-start state,
 // (oin, oout) = step-end state.  neg selects the mu < 0 half-state rule.
-template <int S>
-__host__ __device__ __forceinline__ void cell_step(const LineConst &L, double hd, bool neg, double pin, double pout,
-                                                   double *X, double &oin, double &oout) {
+template <int S, class R>
+__host__ __device__ __forceinline__ void cell_step(const LineConstT<R> &L, R hd, bool neg, R pin, R pout,
+                                                   R *X, R &oin, R &oout) {
   if constexpr (S == SCHEME_BE) {
     cell_be(L, hd, pin, pout, X[0], oin, oout);
     X[0] = oout;
@@ -117,8 +127,8 @@ __host__ __device__ __forceinline__ void cell_step(const LineConst &L, double hd
     X[0] = pout;
     X[1] = oout;
   } else {
-    double a, b, c;
-    const double hup = neg ? X[2] : X[1];
+    R a, b, c;
+    const R hup = neg ? X[2] : X[1];
     cell_bdf2_explicit(L, hd, neg, pin, pout, X[1], X[2], X[3], X[4], X[0], X[0], hup, a, b, c, oin, oout);
     X[0] = pout;
     X[1] = a;
@@ -131,8 +141,8 @@ __host__ __device__ __forceinline__ void cell_step(const LineConst &L, double hd
 // Carried state entering the first cell of a line from per-substep inflow
 // values b[0..3] (solver.cpp:695-697: local_bdry = half_local_bdry =
 // local_bdry_prev_it = bdry_cond).
-template <int S>
-__host__ __device__ __forceinline__ void head_state(const double *b, double *X) {
+template <int S, class R>
+__host__ __device__ __forceinline__ void head_state(const R *b, R *X) {
   if constexpr (S == SCHEME_BE) {
     X[0] = b[0];
   } else if constexpr (S == SCHEME_CN) {
@@ -150,14 +160,14 @@ __host__ __device__ __forceinline__ void head_state(const double *b, double *X) 
 // cell_step for a cell that may be a line head (head_state already applied):
 // in the BDF substep the head sees b[3] as both prev and half upwind node.
 // With equal inflows (non-reflective boundaries) this equals cell_step.
-template <int S>
-__host__ __device__ __forceinline__ void cell_step_maybe_head(const LineConst &L, double hd, bool neg, double pin,
-                                                              double pout, double *X, bool head, double b3,
-                                                              double &oin, double &oout) {
+template <int S, class R>
+__host__ __device__ __forceinline__ void cell_step_maybe_head(const LineConstT<R> &L, R hd, bool neg, R pin,
+                                                              R pout, R *X, bool head, R b3,
+                                                              R &oin, R &oout) {
   if constexpr (S == SCHEME_BDF2) {
-    double a, b, c;
-    const double hup = head ? b3 : (neg ? X[2] : X[1]);
-    const double xp3 = head ? b3 : X[0];
+    R a, b, c;
+    const R hup = head ? b3 : (neg ? X[2] : X[1]);
+    const R xp3 = head ? b3 : X[0];
     cell_bdf2_explicit(L, hd, neg, pin, pout, X[1], X[2], X[3], X[4], X[0], xp3, hup, a, b, c, oin, oout);
     X[0] = pout;
     X[1] = a;
@@ -281,26 +291,27 @@ __host__ __device__ __forceinline__ void map_apply(const double *W, const double
 
 // The per-line affine cell map (cell.hpp, map_apply): coefficients from
 // cell_step<S> on unit inputs (constants and data zeroed), constants from
-// cell_step<S> on zero inputs.  Every coefficient outside the structural
+// cell_step<S> on zero inputs, all in the format R of the line constants (long double on
+// the host's setup path) and rounded to double once.  Every coefficient outside the structural
 // pattern must come out exactly zero; false otherwise.
 // (host code: rtsn_lines.hip builds every line's maps with it, tools/cell_map_check.cpp tests it.)
 // HEAD: the reflective mu > 0 head cell's map instead (cell_step_maybe_head with the
 // mirror's last-substep outflow b3 = X[K-1], the carried state being head_state(b): a map
 // of the same structure, so the kernels run the head cell as the same FMA rows as every
 // other cell -- no divergent per-tick branch into the reference's algebra).
-template <int S, bool HEAD = false>
-inline bool cell_map(const LineConst &Lin, double hd, bool neg, double *W) {
+template <int S, bool HEAD = false, class R = double>
+inline bool cell_map(const LineConstT<R> &Lin, R hd, bool neg, double *W) {
   constexpr int K = SchemeDim<S>::K;
-  double dense[K + 1][K + 3];  // [row][input 0..K+1, constant K+2]
+  R dense[K + 1][K + 3];  // [row][input 0..K+1, constant K+2]
   for (int col = 0; col <= K + 2; ++col) {
-    LineConst L = Lin;
-    if (col != K + 2) L.c[LC_SC] = 0.0;
-    double X[K] = {};
-    double pin = 0.0, pout = 0.0;
-    if (col < K) X[col] = 1.0;
-    if (col == K) pin = 1.0;
-    if (col == K + 1) pout = 1.0;
-    double oi, oo;
+    LineConstT<R> L = Lin;
+    if (col != K + 2) L.c[LC_SC] = R(0.0);
+    R X[K] = {};
+    R pin = R(0.0), pout = R(0.0);
+    if (col < K) X[col] = R(1.0);
+    if (col == K) pin = R(1.0);
+    if (col == K + 1) pout = R(1.0);
+    R oi, oo;
     if constexpr (HEAD)
       cell_step_maybe_head<S>(L, hd, neg, pin, pout, X, true, X[K - 1], oi, oo);
     else
@@ -314,8 +325,8 @@ inline bool cell_map(const LineConst &Lin, double hd, bool neg, double *W) {
       const bool copy = map_copy_row0<S>() && r == 0;
       const bool used = !copy && (col == K + 2 || map_dep<S>(r, col));
       if (used) {
-        W[map_slot<S>(r, col)] = dense[r][col];
-      } else if (dense[r][col] != (copy && col == K + 1 ? 1.0 : 0.0)) {
+        W[map_slot<S>(r, col)] = static_cast<double>(dense[r][col]);  // the one rounding of a coefficient
+      } else if (dense[r][col] != (copy && col == K + 1 ? R(1.0) : R(0.0))) {
         return false;
       }
     }

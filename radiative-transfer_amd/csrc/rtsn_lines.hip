@@ -21,50 +21,56 @@ static int line_direction(int H, int half, int ip) { return half == 0 ? H - 1 - 
 
 // unit_B: the source for B_g = 1 (material coupling scales it per cell).  gt, dx: the medium
 // (the handle's own, or one region's: rtsn_regions.hip)
-static LineConst line_constants(const rt_solver &s, int i, int g, bool unit_B, const phys::GroupTable &gt,
-                                double dx) {
+// In long double (the inputs are doubles, cast exactly): the constants and the map probed from
+// them (cell.hpp cell_map) are rounded to double once, as map coefficients.  Formed in double,
+// a coefficient that cancels lost digits for good -- at c dt / dx = 1e4 the CN map's were up to
+// 2e3 eps off, and every cell and step repeated the error.
+static LineConstT<long double> line_constants(const rt_solver &s, int i, int g, bool unit_B,
+                                              const phys::GroupTable &gt, double dx) {
+  using real = long double;
   const rt_params &p = s.p;
-  const double c = phys::kLight;
-  const double dt = p.dt;
-  const double tau = (p.ts_method == 3) ? dt / 2.0 : dt;
-  const double mu = s.mu[i], m = std::fabs(mu);
-  const double sigma = gt.rho[g] * gt.kappa[g];
-  LineConst L{};
-  const double half = 0.5 * c * tau * dx;
+  const real c = phys::kLight;
+  const real dt = p.dt;
+  const real tau = (p.ts_method == 3) ? dt / real(2.0) : dt;
+  const real mu = s.mu[i], m = std::fabs(mu);
+  const real sigma = real(gt.rho[g]) * gt.kappa[g];
+  LineConstT<real> L{};
+  const real half = real(0.5) * c * tau * dx;
   // S = 1/2 c tau dx (sigma B_g + total_correction), psi = (e_in + e_out)/2
-  L.c[LC_SC] = half * sigma * (unit_B ? 1.0 : gt.B[g]);
-  L.c[LC_SL] = 0.0;
+  L.c[LC_SC] = half * sigma * (unit_B ? real(1.0) : gt.B[g]);
+  L.c[LC_SL] = real(0.0);
   if (p.use_correction) {
-    const double beta = p.V / c;
+    const real beta = p.V / c;
     L.c[LC_SC] += half * ((gt.cor2[g] * mu) * beta - gt.cor3[g] * (mu * mu) * (beta * beta));
-    L.c[LC_SL] = half * gt.cor1[g] * mu * beta * 0.5;
+    L.c[LC_SL] = half * gt.cor1[g] * mu * beta * real(0.5);
   }
-  auto inverse = [](double d, double o, double &i0, double &i1) {
-    const double det = d * d + o * o;
+  auto inverse = [](real d, real o, real &i0, real &i1) {
+    const real det = d * d + o * o;
     i0 = d / det;
     i1 = o / det;
   };
   {  // BE(tau)
-    const double a = 1.0 + c * tau * sigma, b = c * tau * m;
+    const real a = real(1.0) + c * tau * sigma, b = c * tau * m;
     L.c[LC_BE_B] = b;
-    inverse((a * dx + b) / 2.0, b / 2.0, L.c[LC_BE_I0], L.c[LC_BE_I1]);
+    inverse((a * dx + b) / real(2.0), b / real(2.0), L.c[LC_BE_I0], L.c[LC_BE_I1]);
   }
   {  // CN(tau)
-    const double t = 0.5 * c * tau * sigma, A = 0.5 * c * m * tau;
-    const double Bp = 1.0 + t, Cp = 1.0 - t;
+    const real t = real(0.5) * c * tau * sigma, A = real(0.5) * c * m * tau;
+    const real Bp = real(1.0) + t, Cp = real(1.0) - t;
     L.c[LC_CN_A] = A;
-    L.c[LC_CN_K1] = 0.5 * (Cp * dx - A);
-    L.c[LC_CN_K2] = 0.5 * A;
-    inverse(0.5 * (A + Bp * dx), A / 2.0, L.c[LC_CN_I0], L.c[LC_CN_I1]);
+    L.c[LC_CN_K1] = real(0.5) * (Cp * dx - A);
+    L.c[LC_CN_K2] = real(0.5) * A;
+    inverse(real(0.5) * (A + Bp * dx), A / real(2.0), L.c[LC_CN_I0], L.c[LC_CN_I1]);
   }
   {  // BDF(tau) with const_B from the full dt
-    const double t = c * sigma * tau / 6.0, Ab = 1.0 + t, Bc = c * m * dt / 6.0, Cb = 1.0 - 4.0 * t, D = t;
+    const real t = c * sigma * tau / real(6.0), Ab = real(1.0) + t, Bc = c * m * dt / real(6.0);
+    const real Cb = real(1.0) - real(4.0) * t, D = t;
     L.c[LC_BD_BC] = Bc;
-    L.c[LC_BD_Q1] = 0.5 * (Cb * dx - 4.0 * Bc);
-    L.c[LC_BD_Q2] = 2.0 * Bc;
-    L.c[LC_BD_Q3] = 0.5 * (Bc + D * dx);
-    L.c[LC_BD_Q4] = 0.5 * Bc;
-    inverse(0.5 * (Ab * dx + Bc), 0.5 * Bc, L.c[LC_BD_I0], L.c[LC_BD_I1]);
+    L.c[LC_BD_Q1] = real(0.5) * (Cb * dx - real(4.0) * Bc);
+    L.c[LC_BD_Q2] = real(2.0) * Bc;
+    L.c[LC_BD_Q3] = real(0.5) * (Bc + D * dx);
+    L.c[LC_BD_Q4] = real(0.5) * Bc;
+    inverse(real(0.5) * (Ab * dx + Bc), real(0.5) * Bc, L.c[LC_BD_I0], L.c[LC_BD_I1]);
   }
   return L;
 }
@@ -172,7 +178,7 @@ template <int S>
 bool rtsn_detail::medium_maps(const rt_solver *s, bool unit_B, const phys::GroupTable &gt, double dx, double *map,
                               double *hmap) {
   constexpr int WN = map_count<S>();
-  const double hd = 0.5 * dx;
+  const long double hd = 0.5L * dx;
   const size_t Lp = s->Lpad;
   // lines are independent: chunks of them on the host workers (phys::parallel_for)
   const long long lines = 2LL * s->Gl * s->H;
@@ -186,7 +192,7 @@ bool rtsn_detail::medium_maps(const rt_solver *s, bool unit_B, const phys::Group
       const int gl = rem / s->H, ip = rem % s->H;
       const int i = line_direction(s->H, half, ip), g = s->g_lo + gl;
       const size_t ell = ip + static_cast<size_t>(s->H) * gl;
-      const LineConst L = line_constants(*s, i, g, unit_B, gt, dx);
+      const LineConstT<long double> L = line_constants(*s, i, g, unit_B, gt, dx);
       if (!cell_map<S>(L, hd, half == 0, W)) bad = true;
       for (int n = 0; n < WN; ++n) map[(half * WN + n) * Lp + ell] = W[n];
       if (half == 1 && hmap) {

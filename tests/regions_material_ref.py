@@ -3,7 +3,7 @@
 
 One coupled step, per cell x with its own sigma_g(x), rho_cv(x) and dx(x):
 
-* the sweep is test_regions_gpu.RegionReference's (fused_np.LineSet's cell algebra, the mu < 0
+* the sweep is regions_reference.RegionReference's (fused_np.LineSet's cell algebra, the mu < 0
   half mirrored), on the LineSets of the UNIT source -- B_g = 1, correction off -- one per
   region, with the constant Sc multiplied per cell by the step's emission Beff[x, g];
 * B_g(T), dB_g/dT(T) per cell from the C oracle's planck_cell / planck_cell_dBdT (the last
@@ -27,7 +27,7 @@ import copy
 
 import numpy as np
 
-from test_regions_gpu import RegionReference
+from regions_reference import RegionReference
 
 NEWTON_FRAC = 0.25
 

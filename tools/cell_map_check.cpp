@@ -5,7 +5,10 @@
 // map bitwise before head_map_first<S>() -- the rows the wavefront kernels share between the
 // head lane and the others -- and (3) both maps reproduce the algebra they were probed from
 // (cell_step, cell_step_maybe_head with the mirror's last-substep outflow X[K-1]) on random
-// inputs to rounding.  Host code only; tests/test_host.py builds it under ASan + UBSan.
+// inputs to rounding.  Each in double and in long double: the library's setup probes in long
+// double (rtsn_lines.hip) and rounds every coefficient to double once, so there the double
+// map applied to double inputs is held against the long double algebra.
+// Host code only; tests/test_host.py builds it under ASan + UBSan.
 //   g++ -std=c++17 -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include -I radiative-transfer_amd/csrc \
 //       tools/cell_map_check.cpp -o /tmp/cell_map_check && /tmp/cell_map_check
 #include <cmath>
@@ -33,24 +36,26 @@ void expect_close(double a, double b, const char *what, int S) {
   }
 }
 
-template <int S>
+// R: the format the map is probed in (the algebra's, cell.hpp)
+template <int S, class R>
 void check(int lines) {
   constexpr int K = SchemeDim<S>::K, WN = map_count<S>(), F = head_map_first<S>();
   for (int n = 0; n < lines; ++n) {
-    LineConst L;
-    for (double &c : L.c) c = uni(0.1, 2.0);
-    const double hd = uni(1e-4, 0.5);
+    LineConstT<R> L;
+    for (R &c : L.c) c = uni(0.1, 2.0);
+    const R hd = uni(1e-4, 0.5);
     for (int neg = 0; neg < 2; ++neg) {
       double W[WN];
       if (!cell_map<S>(L, hd, neg != 0, W)) {
         if (fails++ < 10) std::printf("scheme %d: line map not of the structural pattern\n", S);
         continue;
       }
-      double X[K], Xc[K], Xn[K], oi, oo, ai, ao;
-      for (int r = 0; r < K; ++r) X[r] = Xc[r] = uni(-1.0, 1.0);
+      double X[K], Xn[K], oi, oo;
+      R Xc[K], ai, ao;
+      for (int r = 0; r < K; ++r) Xc[r] = X[r] = uni(-1.0, 1.0);
       const double pin = uni(-1.0, 1.0), pout = uni(-1.0, 1.0);
       map_apply<S, true>(W, X, pin, pout, Xn, oi, oo);
-      cell_step<S>(L, hd, neg != 0, pin, pout, Xc, ai, ao);
+      cell_step<S>(L, hd, neg != 0, R(pin), R(pout), Xc, ai, ao);
       for (int r = 0; r < K; ++r) expect_close(Xn[r], Xc[r], "line map X'", S);
       expect_close(oi, ai, "line map oin", S);
       expect_close(oo, ao, "line map oout", S);
@@ -65,11 +70,11 @@ void check(int lines) {
         if (Wh[s] != W[s]) {
           if (fails++ < 10) std::printf("scheme %d: head map slot %d differs from the line map\n", S, s);
         }
-      for (int r = 0; r < K; ++r) X[r] = Xc[r] = uni(-1.0, 1.0);
-      if constexpr (S == SCHEME_BDF2) X[0] = Xc[0] = X[2];  // head_state: p_up = the half inflow
-      if constexpr (S == SCHEME_CN) X[0] = Xc[0] = X[1];
+      for (int r = 0; r < K; ++r) Xc[r] = X[r] = uni(-1.0, 1.0);
+      if constexpr (S == SCHEME_BDF2) Xc[0] = X[0] = X[2];  // head_state: p_up = the half inflow
+      if constexpr (S == SCHEME_CN) Xc[0] = X[0] = X[1];
       map_apply<S, true>(Wh, X, pin, pout, Xn, oi, oo);
-      cell_step_maybe_head<S>(L, hd, false, pin, pout, Xc, true, Xc[K - 1], ai, ao);
+      cell_step_maybe_head<S>(L, hd, false, R(pin), R(pout), Xc, true, Xc[K - 1], ai, ao);
       for (int r = 0; r < K; ++r) expect_close(Xn[r], Xc[r], "head map X'", S);
       expect_close(oi, ai, "head map oin", S);
       expect_close(oo, ao, "head map oout", S);
@@ -81,9 +86,12 @@ void check(int lines) {
 
 int main() {
   const int lines = 2000;
-  check<SCHEME_BE>(lines);
-  check<SCHEME_CN>(lines);
-  check<SCHEME_BDF2>(lines);
-  std::printf("%d random lines per scheme, %d failures, worst relative difference %.3g\n", lines, fails, worst);
+  check<SCHEME_BE, double>(lines);
+  check<SCHEME_CN, double>(lines);
+  check<SCHEME_BDF2, double>(lines);
+  check<SCHEME_BE, long double>(lines);
+  check<SCHEME_CN, long double>(lines);
+  check<SCHEME_BDF2, long double>(lines);
+  std::printf("%d random lines per scheme and format, %d failures, worst relative difference %.3g\n", lines, fails, worst);
   return fails ? 1 : 0;
 }
