@@ -304,6 +304,12 @@ rt_status rt_sweep_geometry(rt_solver *s, int *workgroups, long long *tiles);
  * Moments kernel where M/2 is 8, 16 or 32: 1 (default) the producer/consumer
  * moments_pc_kernel, 0 the one-wave moments_kernel; bitwise-identical results. */
 rt_status rt_set_moments_form(rt_solver *s, int form);
+/* The cell map of the level-split pipelined BDF2 pass: 0 (default) auto, the lean maps on a
+ * handle whose lines' maps admit them (a source with no psi term: use_correction off or
+ * V = 0; decided on the coefficients), 1 always the full map; bitwise-identical results for
+ * finite states.  rt_get_map_form: the form the next such launch runs, 0 full, 1 lean. */
+rt_status rt_set_map_form(rt_solver *s, int form);
+rt_status rt_get_map_form(rt_solver *s, int *form);
 /* The material coupling's cross-segment correction of the fused angular sums: 0 (default)
  * the closed forms (phi_correction_geo_kernel for BE / CN, phi_correction_rows_kernel for
  * BDF2), 1 the cell-by-cell walk; equal to rounding. */

@@ -206,12 +206,33 @@ __host__ __device__ constexpr bool map_copy_row0() {
   return S != SCHEME_BE;
 }
 
+// Patterns of the BDF2 map.  MAP_FULL is sized for a source with a psi term, S = Sc + Sl
+// (e_in + e_out).  With Sl == 0 (use_correction off, or V = 0) the substep-2 predictor e3
+// feeds nothing: it enters the BDF substep only through src().  MAP_NOPSI_NEG drops row 3
+// (X'3 = e3out) and column 3 (x2) of rows 4 and oin: 20 FMAs.  On mu > 0 lines the half
+// state is the BE predictor, so the CN result feeds only e3: MAP_NOPSI_POS also drops row 2
+// and column 2 (xh): 13 FMAs.  The surviving FMAs keep MAP_FULL's order, and every dropped
+// one had a zero coefficient (map_admits, checked per line on the host), so for finite
+// states the lean forms are bitwise MAP_FULL on the live rows.
+enum MapPattern { MAP_FULL = 0, MAP_NOPSI_NEG = 1, MAP_NOPSI_POS = 2 };
+
+// is component r of the carried state (input column r / output row r, r < K) kept by pattern P?
+template <int S, int P = MAP_FULL>
+__host__ __device__ constexpr bool map_live(int r) {
+  if (S != SCHEME_BDF2 || P == MAP_FULL) return true;
+  if (r == 3) return false;
+  if (P == MAP_NOPSI_POS && r == 2) return false;
+  return true;
+}
+
 // does output row r (0..K) depend on input c (0..K+1)?
-template <int S>
+template <int S, int P = MAP_FULL>
 __host__ __device__ constexpr bool map_dep(int r, int c) {
   constexpr int K = SchemeDim<S>::K;
   if (map_copy_row0<S>() && r == 0) return false;
+  if (r < K && !map_live<S, P>(r)) return false;
   if (c >= K) return true;  // pin, pout feed every computed row
+  if (!map_live<S, P>(c)) return false;
   if constexpr (S == SCHEME_BDF2) {
     if (r == 1) return c == 1;
     if (r == 2) return c <= 2;
@@ -221,15 +242,21 @@ __host__ __device__ constexpr bool map_dep(int r, int c) {
   return true;
 }
 
+// is output row r (0..K) computed (not the copy row, not dropped by the pattern)?
+template <int S, int P = MAP_FULL>
+__host__ __device__ constexpr bool map_row(int r) {
+  return !(map_copy_row0<S>() && r == 0) && (r >= SchemeDim<S>::K || map_live<S, P>(r));
+}
+
 // slot of coefficient (r, c) in the packed map; the constant of row r follows its coefficients
-template <int S>
+template <int S, int P = MAP_FULL>
 __host__ __device__ constexpr int map_slot(int r, int c) {
   constexpr int K = SchemeDim<S>::K;
   int n = 0;
   for (int rr = 0; rr <= K; ++rr) {
-    if (map_copy_row0<S>() && rr == 0) continue;
+    if (!map_row<S, P>(rr)) continue;
     for (int cc = 0; cc < K + 2; ++cc) {
-      if (!map_dep<S>(rr, cc)) continue;
+      if (!map_dep<S, P>(rr, cc)) continue;
       if (rr == r && cc == c) return n;
       ++n;
     }
@@ -239,10 +266,53 @@ __host__ __device__ constexpr int map_slot(int r, int c) {
   return -1;
 }
 
-template <int S>
+template <int S, int P = MAP_FULL>
 __host__ __device__ constexpr int map_count() {
   constexpr int K = SchemeDim<S>::K;
-  return map_slot<S>(K, K + 2) + 1;
+  return map_slot<S, P>(K, K + 2) + 1;
+}
+
+// FMAs of one application of the map: its coefficients without the rows' constants
+template <int S, int P = MAP_FULL>
+__host__ __device__ constexpr int map_fmas() {
+  int rows = 0;
+  for (int r = 0; r <= SchemeDim<S>::K; ++r) rows += map_row<S, P>(r) ? 1 : 0;
+  return map_count<S, P>() - rows;
+}
+
+// The lean pattern the level-split pass runs on each half's lines, and the rows of the two
+// packed lean maps back to back (mu < 0 lines first).
+__host__ __device__ constexpr int lean_pattern(bool neg) { return neg ? MAP_NOPSI_NEG : MAP_NOPSI_POS; }
+__host__ __device__ constexpr int lean_map_rows() {
+  return map_count<SCHEME_BDF2, lean_pattern(true)>() + map_count<SCHEME_BDF2, lean_pattern(false)>();
+}
+
+// Does a line's MAP_FULL map W admit the lean pattern of its half (neg: MAP_NOPSI_NEG, else
+// MAP_NOPSI_POS)?  The dropped rows feed the live ones only through the dropped columns of
+// the BDF substep's rows (K - 1 and oin), so those coefficients being zero is the whole test.
+template <int S>
+inline bool map_admits(const double *W, bool neg) {
+  if constexpr (S != SCHEME_BDF2) {
+    return false;
+  } else {
+    constexpr int K = SchemeDim<S>::K;
+    for (int r = K - 1; r <= K; ++r) {
+      if (W[map_slot<S>(r, 3)] != 0.0) return false;
+      if (!neg && W[map_slot<S>(r, 2)] != 0.0) return false;
+    }
+    return true;
+  }
+}
+
+// the lean map of pattern P from a MAP_FULL map: its surviving coefficients, packed
+template <int S, int P>
+inline void map_pack(const double *W, double *Wp) {
+  constexpr int K = SchemeDim<S>::K;
+  for (int r = 0; r <= K; ++r) {
+    if (!map_row<S, P>(r)) continue;
+    for (int c = 0; c <= K + 2; ++c)
+      if (c == K + 2 || map_dep<S, P>(r, c)) Wp[map_slot<S, P>(r, c)] = W[map_slot<S>(r, c)];
+  }
 }
 
 // The reflective mu > 0 head cell's map (cell_step_maybe_head probed the same way) differs
@@ -261,8 +331,9 @@ __host__ __device__ constexpr int head_map_first() {
 // (both 0.0; fma(w, 0.0, acc) is not folded by the compiler), ZERO0 also skips X[0]
 // (0.0 after one cell where row 0 copies dout: CN, BDF2) -- the same values.  ROW_LO > 0:
 // only rows ROW_LO .. K (Xn below ROW_LO untouched), each the same FMA sequence as in the
-// whole map -- the reflective head lane redoing the rows where its map differs.
-template <int S, bool CONST, bool NODATA = false, bool ZERO0 = false, int ROW_LO = 0>
+// whole map -- the reflective head lane redoing the rows where its map differs.  P: W is the
+// packed map of that pattern; the rows it drops leave their Xn entry untouched.
+template <int S, bool CONST, bool NODATA = false, bool ZERO0 = false, int ROW_LO = 0, int P = MAP_FULL>
 __host__ __device__ __forceinline__ void map_apply(const double *W, const double *X, double din, double dout,
                                                    double *Xn, double &oin, double &oout, double cs = 1.0) {
   constexpr int K = SchemeDim<S>::K;
@@ -273,13 +344,14 @@ __host__ __device__ __forceinline__ void map_apply(const double *W, const double
       Xn[0] = dout;
       continue;
     }
-    double acc = CONST ? W[map_slot<S>(r, K + 2)] * cs : 0.0;
+    if (!map_row<S, P>(r)) continue;
+    double acc = CONST ? W[map_slot<S, P>(r, K + 2)] * cs : 0.0;
 #pragma unroll
     for (int c = 0; c < K + 2; ++c) {
-      if (!map_dep<S>(r, c)) continue;
+      if (!map_dep<S, P>(r, c)) continue;
       if ((NODATA && c >= K) || (ZERO0 && c == 0)) continue;
       const double u = c < K ? X[c] : (c == K ? din : dout);
-      acc = fma(W[map_slot<S>(r, c)], u, acc);
+      acc = fma(W[map_slot<S, P>(r, c)], u, acc);
     }
     if (r < K)
       Xn[r] = acc;

@@ -65,6 +65,10 @@ struct SegArgs {
   // [nregions][2][map_count<S>][Lpad], and lane_region[half][lanes] the region chain lane j's
   // cells lie in (the mu < 0 half's table the mirror image of the mu > 0 one)
   const int *lane_region;     // nullptr: one medium
+  // level-split pipelined pass only (kernels_split.hip): the lean maps of a handle whose source
+  // has no psi term, [lean_map_rows()][Lpad]: the mu < 0 lines' packed rows, then the mu > 0
+  // lines' (cell.hpp, lean_pattern)
+  const double *lmap;         // nullptr: the full map
 };
 
 struct FoldArgs {

@@ -1,6 +1,7 @@
 // kernels_split.hip -- the level-split pipelined pass (sweep_split_kernel): a BDF2
 // segment's T levels shared by 2 or 4 waves of a workgroup.  Its own translation unit
-// (the kernel is instantiated for 14 (T, waves) pairs, the tail variant for 9) so it compiles beside kernels.hip.
+// (the kernel is instantiated for 14 (T, waves) pairs, the tail variant for 9, each on the full
+// and on the lean cell maps) so it compiles beside kernels.hip.
 #include <hip/hip_runtime.h>
 
 #include "cell.hpp"
@@ -31,7 +32,9 @@ namespace rtamd {
 // ------------------------------------------------------------------------
 // TAIL: the wave runs only its first nl of the TW levels (wave-uniform), the rest pass the
 // nodes through unchanged -- the run's last n mod T steps as a pipelined block (tail_levels).
-template <int S, int TW, int C, bool IN_HBM, bool OUT_HBM, bool LASTCH, bool TAIL>
+// P: the map's pattern (cell.hpp): W is that pattern's packed map, and the carried-state
+// components it drops are neither read nor written.
+template <int S, int TW, int C, bool IN_HBM, bool OUT_HBM, bool LASTCH, bool TAIL, int P>
 __device__ __forceinline__ void split_chunk(const double *W, double (&ein)[C], double (&eout)[C],
                                             double (&X)[TW][SchemeDim<S>::K], bool head, double h_oi, double h_oo,
                                             const double2 *lin, double2 *lout, __amdgpu_buffer_rsrc_t Rw,
@@ -51,9 +54,10 @@ __device__ __forceinline__ void split_chunk(const double *W, double (&ein)[C], d
         if constexpr (TAIL)
           if (t >= nl) break;
         double Xn[K], a, e;
-        map_apply<S, true>(W, X[t], oi, oo, Xn, a, e);
+        map_apply<S, true, false, false, 0, P>(W, X[t], oi, oo, Xn, a, e);
 #pragma unroll
-        for (int r = 0; r < K; ++r) X[t][r] = Xn[r];
+        for (int r = 0; r < K; ++r)
+          if (map_live<S, P>(r)) X[t][r] = Xn[r];
         oi = a;
         oo = e;
       }
@@ -76,7 +80,7 @@ __device__ __forceinline__ void split_chunk(const double *W, double (&ein)[C], d
         eout[rr] = v.y;
       }
       // each load after its cell's FMAs (left alone, the scheduler sinks them to the end)
-      __builtin_amdgcn_sched_group_barrier(0x002, TW * 28, 0);  // VALU
+      __builtin_amdgcn_sched_group_barrier(0x002, TW * map_fmas<S, P>(), 0);  // VALU
       __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);        // VMEM read
     } else if constexpr (!LASTCH) {  // refill with the next chunk from the previous wave
       const double2 v = lin[c * 64 + lane];
@@ -97,20 +101,8 @@ __device__ __forceinline__ constexpr int split_tw() {
   return T / KW;
 }
 
-// Wave w's role (compile time: with the role a runtime branch inside one body the
-// allocation measured ~340 registers, each role alone ~215).
-template <int S, int T, int KW, int w, bool TAIL>
-__device__ __forceinline__ void split_role(const SegArgs &a, double2 (*hand)[2][split_chunk_cells() * 64],
-                                           double2 *hhead) {
-  constexpr int K = SchemeDim<S>::K;
-  constexpr int TW = split_tw<T, KW, w>();  // levels [t0, t0 + TW)
-  constexpr int WN = map_count<S>();
-  constexpr int C = split_chunk_cells();
-  constexpr bool IN = w == 0, OUT = w == KW - 1;
-  const int lane = threadIdx.x & 63;
-  constexpr int t0 = split_t0<T, KW, w>();  // this wave's first level
-  const size_t stride = static_cast<size_t>(a.Lpad);
-  int half, s, q, pos;
+// The workgroup's half, segment, line group and chain position (workgroup-uniform).
+__device__ __forceinline__ void split_decode(const SegArgs &a, int &half, int &s, int &q, int &pos) {
   if (a.reflective) {
     pos = a.pos_lo + static_cast<int>(blockIdx.x) / a.Q;
     q = static_cast<int>(blockIdx.x) % a.Q;
@@ -124,6 +116,26 @@ __device__ __forceinline__ void split_role(const SegArgs &a, double2 (*hand)[2][
     q = rem % a.Q;
     s = pos;
   }
+}
+
+// Wave w's role (compile time: with the role a runtime branch inside one body the
+// allocation measured ~340 registers, each role alone ~215).  P: the map's pattern; a lean
+// role loads and computes only the pattern's components of the carried states and stores 0.0
+// into the others at exit, which a full-form kernel continuing the handle multiplies by its
+// zero coefficients.
+template <int S, int T, int KW, int w, bool TAIL, int P>
+__device__ __forceinline__ void split_role(const SegArgs &a, double2 (*hand)[2][split_chunk_cells() * 64],
+                                           double2 *hhead) {
+  constexpr int K = SchemeDim<S>::K;
+  constexpr int TW = split_tw<T, KW, w>();  // levels [t0, t0 + TW)
+  constexpr int WN = map_count<S, P>();
+  constexpr int C = split_chunk_cells();
+  constexpr bool IN = w == 0, OUT = w == KW - 1;
+  const int lane = threadIdx.x & 63;
+  constexpr int t0 = split_t0<T, KW, w>();  // this wave's first level
+  const size_t stride = static_cast<size_t>(a.Lpad);
+  int half, s, q, pos;
+  split_decode(a, half, s, q, pos);
   const int slot = (a.pass_lo - (pos - a.pos_lo)) & 1;
   // TAIL: position pos_lo's block is a.tail_levels < T levels (layout and carried states
   // still T's); every other position runs all T
@@ -166,7 +178,7 @@ __device__ __forceinline__ void split_role(const SegArgs &a, double2 (*hand)[2][
 #pragma unroll
     for (int t = 0; t < TW; ++t)
 #pragma unroll
-      for (int r = 0; r < K; ++r) X[t][r] = up[((t0 + t) * K + r) * stride];
+      for (int r = 0; r < K; ++r) X[t][r] = map_live<S, P>(r) ? up[((t0 + t) * K + r) * stride] : 0.0;
   }
 
   // ---- rows: wave 0 streams them in, the last wave stores them ----
@@ -218,7 +230,12 @@ __device__ __forceinline__ void split_role(const SegArgs &a, double2 (*hand)[2][
 
   double W[WN];
 #pragma unroll
-  for (int n = 0; n < WN; ++n) W[n] = a.map[(static_cast<size_t>(half) * WN + n) * stride + ell];
+  for (int n = 0; n < WN; ++n) {
+    if constexpr (P == MAP_FULL)
+      W[n] = a.map[(static_cast<size_t>(half) * WN + n) * stride + ell];
+    else  // the half's packed lean map: the mu > 0 lines' rows follow the mu < 0 lines'
+      W[n] = a.lmap[(static_cast<size_t>(half) * map_count<S, lean_pattern(true)>() + n) * stride + ell];
+  }
   // every prologue load (map, carried states, chunk 0) complete before the chunks start:
   // the wait-count pass merges the loop's entry into its head, and a map load still
   // pending there made EVERY chunk start wait for all loads in flight (vmcnt(0)) -- the
@@ -243,20 +260,20 @@ __device__ __forceinline__ void split_role(const SegArgs &a, double2 (*hand)[2][
   }
   int k0 = k_begin;
   for (int m = 0; m + 1 < nch; ++m, k0 += C) {
-    split_chunk<S, TW, C, IN, OUT, false, TAIL>(W, ein, eout, X, refl_head && m == 0, h_oi, h_oo,
+    split_chunk<S, TW, C, IN, OUT, false, TAIL, P>(W, ein, eout, X, refl_head && m == 0, h_oi, h_oo,
                                                 lin + ((m + 1) & 1) * LB, lout + (m & 1) * LB, rows(k0), rows(k0 + C),
                                                 voff, row_bytes, C, lane, nl);
     __syncthreads();
   }
-  split_chunk<S, TW, C, IN, OUT, true, TAIL>(W, ein, eout, X, refl_head && nch == 1, h_oi, h_oo, lin,
-                                             lout + ((nch - 1) & 1) * LB, rows(k0), rows(k0), voff, row_bytes,
-                                             k_end - k0, lane, nl);
+  split_chunk<S, TW, C, IN, OUT, true, TAIL, P>(W, ein, eout, X, refl_head && nch == 1, h_oi, h_oo, lin,
+                                                lout + ((nch - 1) & 1) * LB, rows(k0), rows(k0), voff, row_bytes,
+                                                k_end - k0, lane, nl);
   __syncthreads();
   double *ag = a.aggs[slot] + half * half_stride + static_cast<size_t>(s) * seg_stride + ell;
 #pragma unroll
   for (int t = 0; t < TW; ++t)
 #pragma unroll
-    for (int r = 0; r < K; ++r) ag[((t0 + t) * K + r) * stride] = X[t][r];
+    for (int r = 0; r < K; ++r) ag[((t0 + t) * K + r) * stride] = map_live<S, P>(r) ? X[t][r] : 0.0;
   for (int I = 0; I < 2 * (KW - 1 - w); ++I) __syncthreads();  // the later waves drain it
 }
 
@@ -264,38 +281,56 @@ constexpr int kSplitPrioWave = 0;  // the wave given issue priority 1 (wave 0 st
 // Wave w's role; with `tail`, the waves whose levels reach past the tail's take the TAIL body,
 // the others the plain one -- correct only when wave 0's levels all lie inside the tail
 // (tail_levels >= split_tw of wave 0), which launch_split_tail enforces.
-template <int S, int T, int KW, int w>
+template <int S, int T, int KW, int w, int P>
 __device__ __forceinline__ void split_role_of(const SegArgs &a, double2 (*hand)[2][split_chunk_cells() * 64],
                                               double2 *hhead, bool tail) {
   if (tail && a.tail_levels < split_t0<T, KW, w>() + split_tw<T, KW, w>())
-    split_role<S, T, KW, w, true>(a, hand, hhead);
+    split_role<S, T, KW, w, true, P>(a, hand, hhead);
   else
-    split_role<S, T, KW, w, false>(a, hand, hhead);
+    split_role<S, T, KW, w, false, P>(a, hand, hhead);
 }
 
-template <int S, int T, int KW, bool TAIL>
+template <int S, int T, int KW, bool TAIL, int P>
 __device__ __forceinline__ void split_roles(const SegArgs &a, double2 (*hand)[2][split_chunk_cells() * 64],
-                                            double2 *hhead, int w) {
-  bool tail = false;  // workgroup-uniform: this workgroup is position pos_lo's, which runs the tail
-  if constexpr (TAIL) tail = (static_cast<int>(blockIdx.x) % (a.Q * a.npos)) / a.Q == 0;
+                                            double2 *hhead, int w, bool tail) {
+  if constexpr (!TAIL) tail = false;
   if constexpr (KW == 2) {
     if (w == 0)
-      split_role_of<S, T, 2, 0>(a, hand, hhead, tail);
+      split_role_of<S, T, 2, 0, P>(a, hand, hhead, tail);
     else
-      split_role_of<S, T, 2, 1>(a, hand, hhead, tail);
+      split_role_of<S, T, 2, 1, P>(a, hand, hhead, tail);
   } else {
     if (w == 0)
-      split_role_of<S, T, 4, 0>(a, hand, hhead, tail);
+      split_role_of<S, T, 4, 0, P>(a, hand, hhead, tail);
     else if (w == 1)
-      split_role_of<S, T, 4, 1>(a, hand, hhead, tail);
+      split_role_of<S, T, 4, 1, P>(a, hand, hhead, tail);
     else if (w == 2)
-      split_role_of<S, T, 4, 2>(a, hand, hhead, tail);
+      split_role_of<S, T, 4, 2, P>(a, hand, hhead, tail);
     else
-      split_role_of<S, T, 4, 3>(a, hand, hhead, tail);
+      split_role_of<S, T, 4, 3, P>(a, hand, hhead, tail);
   }
 }
 
-template <int S, int T, int KW>
+// The workgroup's form, picked once from what is workgroup-uniform: LEAN kernels (launched
+// for a.lmap, launch_split) run each half's lean pattern, every role still its own
+// compile-time body.
+template <int S, int T, int KW, bool TAIL, bool LEAN>
+__device__ __forceinline__ void split_forms(const SegArgs &a, double2 (*hand)[2][split_chunk_cells() * 64],
+                                            double2 *hhead, int w) {
+  int half, s, q, pos;
+  split_decode(a, half, s, q, pos);
+  const bool tail = pos == a.pos_lo;  // this workgroup is position pos_lo's, which runs the tail
+  if constexpr (!LEAN) {
+    split_roles<S, T, KW, TAIL, MAP_FULL>(a, hand, hhead, w, tail);
+  } else {
+    if (half == 0)
+      split_roles<S, T, KW, TAIL, lean_pattern(true)>(a, hand, hhead, w, tail);
+    else
+      split_roles<S, T, KW, TAIL, lean_pattern(false)>(a, hand, hhead, w, tail);
+  }
+}
+
+template <int S, int T, int KW, bool LEAN = false>
 __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2))) void sweep_split_kernel(SegArgs a) {
   static_assert(T % KW == 0 && (KW == 2 || KW == 4), "levels split evenly over 2 or 4 waves");
   __shared__ double2 hand[KW - 1][2][split_chunk_cells() * 64];  // link w: wave w -> w + 1, chunk m in [m & 1]
@@ -308,7 +343,7 @@ __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // T = 40 pass 7.85-7.88 vs 7.90-7.91 (r03aq_prio.jsonl; MI355X_MICROARCH.md, two waves per
   // SIMD, item 4).
   if (w == kSplitPrioWave) __builtin_amdgcn_s_setprio(1);
-  split_roles<S, T, KW, false>(a, hand, hhead, w);
+  split_forms<S, T, KW, false, LEAN>(a, hand, hhead, w);
 }
 
 // A pipelined launch whose first active position (pos_lo, vacuum lines only) runs the
@@ -317,7 +352,7 @@ __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2)))
 // aligned passes with the cross-segment correction after it.  The tail positions keep T's
 // aggregate layout, so the two kinds share the aggs ring.  Same arithmetic per (cell,
 // level) as every other schedule.
-template <int S, int T, int KW>
+template <int S, int T, int KW, bool LEAN = false>
 __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2))) void sweep_split_tail_kernel(
     SegArgs a) {
   __shared__ double2 hand[KW - 1][2][split_chunk_cells() * 64];
@@ -328,18 +363,25 @@ __global__ __launch_bounds__(64 * KW) __attribute__((amdgpu_waves_per_eu(2, 2)))
   // runtime bound in the level loop the workgroup ran ~55% slower (the loop's pinned loads
   // lose their place), which set every drain launch's time (16-group shard, 100 steps: 237
   // vs 150 ms for 96 steps, gpurun r04ac)
-  split_roles<S, T, KW, true>(a, hand, hhead, w);
+  split_forms<S, T, KW, true, LEAN>(a, hand, hhead, w);
 }
 
+// a.lmap set (a lean-eligible handle, rt_set_map_form auto): the lean kernel, bitwise the full one
 template <int T, int KW>
 static hipError_t launch_split_t(const SegArgs &a, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((sweep_split_kernel<SCHEME_BDF2, T, KW>), dim3(grid), dim3(64 * KW), 0, st, a);
+  if (a.lmap)
+    hipLaunchKernelGGL((sweep_split_kernel<SCHEME_BDF2, T, KW, true>), dim3(grid), dim3(64 * KW), 0, st, a);
+  else
+    hipLaunchKernelGGL((sweep_split_kernel<SCHEME_BDF2, T, KW>), dim3(grid), dim3(64 * KW), 0, st, a);
   return hipGetLastError();
 }
 
 template <int T, int KW>
 static hipError_t launch_split_tail_t(const SegArgs &a, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((sweep_split_tail_kernel<SCHEME_BDF2, T, KW>), dim3(grid), dim3(64 * KW), 0, st, a);
+  if (a.lmap)
+    hipLaunchKernelGGL((sweep_split_tail_kernel<SCHEME_BDF2, T, KW, true>), dim3(grid), dim3(64 * KW), 0, st, a);
+  else
+    hipLaunchKernelGGL((sweep_split_tail_kernel<SCHEME_BDF2, T, KW>), dim3(grid), dim3(64 * KW), 0, st, a);
   return hipGetLastError();
 }
 

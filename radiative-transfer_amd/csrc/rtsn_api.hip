@@ -241,6 +241,7 @@ static rt_status create_impl(const rt_params *pin, int g_lo, int g_hi, int d_lo,
   if (!e) e = dalloc(h->E, sizeof(double2) * 2 * Nrow * Lp);
   if (!e) e = dalloc(h->hmap, sizeof(double) * map_count_of(h->scheme) * Lp);
   if (!e) e = dalloc(h->map, sizeof(double) * 2 * map_count_of(h->scheme) * Lp * std::max<size_t>(1, h->regions.size()));
+  if (!e && h->scheme == SCHEME_BDF2 && !regional(h)) e = dalloc(h->lmap, sizeof(double) * lean_map_rows() * Lp);
   for (int T = 1; T <= kMaxAlignedBlock; ++T)
     if (!e) e = dalloc(h->prop[T], sizeof(double) * 2 * prop_count(K, T) * Lp);
   if (!e) e = dalloc(h->bdry, sizeof(double) * 2 * Lp);
@@ -411,6 +412,19 @@ extern "C" rt_status rt_set_moments_form(rt_solver *s, int form) {
   if (form != 0 && form != 1) return fail(s, RT_ERR_ARG, "rt_set_moments_form: 0 (one wave) or 1 (producer/consumer)");
   s->moments_form = form;
   s->mom_version = 0;  // the next read-out runs the chosen kernel
+  return RT_OK;
+}
+
+extern "C" rt_status rt_set_map_form(rt_solver *s, int form) {
+  if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_map_form: NULL handle");
+  if (form != 0 && form != 1) return fail(s, RT_ERR_ARG, "rt_set_map_form: 0 (auto: lean where eligible) or 1 (full)");
+  s->map_form = form;  // the forms are bitwise equal: a pipeline in flight may change over
+  return RT_OK;
+}
+
+extern "C" rt_status rt_get_map_form(rt_solver *s, int *form) {
+  if (!s || !form) return fail(s, RT_ERR_ARG, "rt_get_map_form: bad argument");
+  *form = lean_maps(s) ? 1 : 0;
   return RT_OK;
 }
 

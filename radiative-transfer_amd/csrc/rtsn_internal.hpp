@@ -243,6 +243,9 @@ struct rt_solver {
   long long transfer_chunk = 0;  // test hook (rt_debug_set_transfer_chunk): doubles per host transfer piece, 0 default
   int moments_form = 1;          // rt_set_moments_form: 1 producer/consumer, 0 one-wave (bitwise equal)
   int phi_corr_form = 0;         // rt_set_phi_correction_form: 0 closed forms, 1 the cell-by-cell walk
+  int map_form = 0;              // rt_set_map_form: 0 auto (the lean maps where eligible), 1 always the full map
+  bool lean_ok = false;          // BDF2 and every real line's map admits its half's lean pattern (line_maps_s)
+  rtsn_detail::DeviceBuf lmap;   // [lean_map_rows()][Lpad] the packed lean maps (valid while lean_ok)
   // material-temperature coupling (rt_material_enable)
   bool material = false;
   double rho_cv = 0.0, wsum = 0.0;  // wsum: this handle's quadrature weights (its q share)
@@ -319,6 +322,12 @@ rt_status fail(rt_solver *s, rt_status st, const std::string &msg);
 void set_last_error(const char *msg);  // the thread's error text alone (host-only units)
 
 inline bool split_block(int T) { return level_split_supported(SCHEME_BDF2, T); }
+
+// Does the next level-split pipelined launch run the lean maps (rt_get_map_form)?  Region
+// and material-coupled handles never do: they do not run that kernel.
+inline bool lean_maps(const rt_solver *s) {
+  return s->lean_ok && s->map_form == 0 && !s->material && s->regions.empty();
+}
 
 // Waves per segment of the pipelined pass: the caller's choice, or by default two waves
 // (sweep_split_kernel) where measured faster -- BDF2 at T = 20, whose one-wave kernel

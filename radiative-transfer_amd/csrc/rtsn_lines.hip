@@ -208,6 +208,9 @@ bool rtsn_detail::medium_maps(const rt_solver *s, bool unit_B, const phys::Group
 }
 
 template <int S>
+static rt_status lean_maps_s(rt_solver *s, const double *map, const double *hmap);
+
+template <int S>
 rt_status rtsn_detail::line_maps_s(rt_solver *s, bool unit_B, DeviceBuf &map_dev, DeviceBuf &hmap_dev) {
   constexpr int WN = map_count<S>();
   const size_t Lp = s->Lpad;
@@ -219,6 +222,44 @@ rt_status rtsn_detail::line_maps_s(rt_solver *s, bool unit_B, DeviceBuf &map_dev
   rt_status st;
   if ((st = upload(s, hmap_dev, hmap.data(), hmap.size() * sizeof(double)))) return st;
   if ((st = upload(s, map_dev, map.data(), map.size() * sizeof(double)))) return st;
+  if (!unit_B) return lean_maps_s<S>(s, map.data(), hmap.data());  // eligibility follows the maps
+  return RT_OK;
+}
+
+// The handle's lean eligibility and packed lean maps from its lines' full maps (cell.hpp,
+// map_admits): BDF2, and every real line of both halves -- padding lanes hold no map --
+// admits its half's lean pattern, a reflective handle's head-cell maps too.  Decided on the
+// coefficients themselves, never on V or use_correction.
+template <int S>
+static rt_status lean_maps_s(rt_solver *s, const double *map, const double *hmap) {
+  s->lean_ok = false;
+  if constexpr (S == SCHEME_BDF2) {
+    constexpr int WN = map_count<S>(), PN = lean_pattern(true), PP = lean_pattern(false);
+    constexpr int NN = map_count<S, PN>();
+    const size_t Lp = s->Lpad, lines = static_cast<size_t>(s->Gl) * s->H;
+    if (!s->lmap.p) return RT_OK;
+    std::vector<double> lmap(static_cast<size_t>(lean_map_rows()) * Lp, 0.0);
+    const bool refl = s->p.bc_left_indicator == 2;
+    for (int half = 0; half < 2; ++half)
+      for (size_t ell = 0; ell < lines; ++ell) {
+        double W[WN], Wh[WN], Wp[WN];
+        for (int n = 0; n < WN; ++n) W[n] = map[(half * WN + n) * Lp + ell];
+        if (!map_admits<S>(W, half == 0)) return RT_OK;
+        if (half == 1 && refl) {
+          for (int n = 0; n < WN; ++n) Wh[n] = hmap[n * Lp + ell];
+          if (!map_admits<S>(Wh, false)) return RT_OK;
+        }
+        if (half == 0) {
+          map_pack<S, PN>(W, Wp);
+          for (int n = 0; n < NN; ++n) lmap[n * Lp + ell] = Wp[n];
+        } else {
+          map_pack<S, PP>(W, Wp);
+          for (int n = 0; n < map_count<S, PP>(); ++n) lmap[(NN + n) * Lp + ell] = Wp[n];
+        }
+      }
+    if (rt_status st = upload(s, s->lmap, lmap.data(), lmap.size() * sizeof(double))) return st;
+    s->lean_ok = true;
+  }
   return RT_OK;
 }
 

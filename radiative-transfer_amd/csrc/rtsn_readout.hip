@@ -505,7 +505,10 @@ extern "C" rt_status rt_sweep_flops(rt_solver *s, double *flops_per_launch) {
   // one FMA per structural coefficient of the cell map (cell.hpp): the
   // affine constants are the accumulators' initial values, not extra ops
   const int rows = s->K + 1 - (s->scheme == SCHEME_BE ? 0 : 1);
-  const double fma = static_cast<double>(map_count_of(s->scheme) - rows);
+  double fma = static_cast<double>(map_count_of(s->scheme) - rows);
+  // a lean level-split pass (cell.hpp: lean_pattern): half the lines on each half's pattern
+  if (lean_maps(s) && level_waves_of(s, s->T) != 1)
+    fma = 0.5 * (map_fmas<SCHEME_BDF2, lean_pattern(true)>() + map_fmas<SCHEME_BDF2, lean_pattern(false)>());
   *flops_per_launch = 2.0 * fma * s->T * static_cast<double>(s->p.M) * s->Gl * s->p.N;
   return RT_OK;
 }

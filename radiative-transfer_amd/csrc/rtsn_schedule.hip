@@ -262,6 +262,7 @@ static rt_status pipe_launch(rt_solver *s) {
     const int grid = a.npos * per_pos;
     a.level_waves = fill_level_waves(s, grid);
     a.tail_levels = block(c0) == T ? 0 : s->tail;  // only the first position can run the tail
+    a.lmap = lean_maps(s) ? static_cast<const double *>(s->lmap.p) : nullptr;  // (read by the split kernels only)
     hipEvent_t e1;
     rt_status st = event_begin(s, &e1);
     if (st) return st;

@@ -138,6 +138,8 @@ def lib():
         L.rt_set_segmentation.argtypes = [vp, C.c_int]
         L.rt_set_moments_form.argtypes = [vp, C.c_int]
         L.rt_set_phi_correction_form.argtypes = [vp, C.c_int]
+        L.rt_set_map_form.argtypes = [vp, C.c_int]
+        L.rt_get_map_form.argtypes = [vp, C.POINTER(C.c_int)]
         L.rt_debug_fail_launch.argtypes = [vp, C.c_int]
         L.rt_debug_set_transfer_chunk.argtypes = [vp, C.c_longlong]
         L.rt_get_level_waves.argtypes = [vp, C.POINTER(C.c_int)]
@@ -738,6 +740,18 @@ class Solver:
     def set_moments_form(self, form: int):
         """rt_set_moments_form: 1 producer/consumer (default), 0 one-wave moments kernel."""
         _check(lib().rt_set_moments_form(self._h, int(form)), "rt_set_moments_form", self._h)
+
+    @property
+    def map_form(self) -> int:
+        """rt_get_map_form: the cell map the next level-split pipelined launch runs, 0 full, 1 lean.
+        Set (rt_set_map_form): 0 auto (lean where the handle is eligible, the default), 1 always full."""
+        v = C.c_int(0)
+        _check(lib().rt_get_map_form(self._h, C.byref(v)), "rt_get_map_form", self._h)
+        return v.value
+
+    @map_form.setter
+    def map_form(self, form: int):
+        _check(lib().rt_set_map_form(self._h, int(form)), "rt_set_map_form", self._h)
 
     def set_phi_correction_form(self, form: int):
         """rt_set_phi_correction_form: 0 closed forms (default), 1 the cell-by-cell walk."""
