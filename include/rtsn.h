@@ -323,6 +323,12 @@ rt_status rt_debug_fail_launch(rt_solver *s, int after);
  * chunks and 16 MB pinned pieces; moments then come in one transfer per state): the chunk
  * edges of rt_get_psi / rt_get_ends / rt_set_ends and the staged moments, for testing. */
 rt_status rt_debug_set_transfer_chunk(rt_solver *s, long long doubles);
+/* A region handle in segment mode (else RT_ERR_STATE): plan the segments for `cells` cells per
+ * segment (rt_regions_plan_segments' target_cells) instead of the target rt_set_segmentation
+ * gives (0: that target again), for testing -- a short line gets the fewest, 16-cell segments
+ * from any workgroups-per-CU target.  Applied as rt_set_segmentation is: now if every chain
+ * position is at the same time, else before the next pipeline starts. */
+rt_status rt_debug_set_segment_cells(rt_solver *s, int cells);
 
 /* ---- material-temperature coupling (beyond the reference) ---------------
  * The reference holds T constant (solver.cpp:157).  With coupling enabled the
@@ -407,12 +413,20 @@ rt_status rt_get_material_transit(rt_solver *s, double *E);
 /* ---- multi-region slabs (beyond the reference) ----------------------------
  * The reference's medium is uniform: one rho, one kappa_g table, one T and one dx
  * (solver.cpp:157).  A region handle holds a slab of piecewise-constant regions, listed left
- * to right, each with its own density, opacity, temperature and mesh width.  It always runs
- * the short-line wavefront (rt_set_wavefront): a chain lane's C cells lie in one region and
- * the lane holds that region's cell map, so the tick loop is the uniform chain's.  Admissible
- * C are those of 1, 2, 4, 8 that divide every region's first cell and N; lines of up to 512
- * cells (256 with the reflective left boundary) fit at C = 1, up to 4096 (2048) with region
- * edges on multiples of 8. */
+ * to right, each with its own density, opacity, temperature and mesh width.  It runs in one
+ * of two modes.
+ * Chain mode (the default where a chain fits): the short-line wavefront (rt_set_wavefront); a
+ * chain lane's C cells lie in one region and the lane holds that region's cell map, so the
+ * tick loop is the uniform chain's.  Admissible C are those of 1, 2, 4, 8 that divide every
+ * region's first cell and N; lines of up to 512 cells (256 with the reflective left boundary)
+ * fit at C = 1, up to 4096 (2048) with region edges on multiples of 8.
+ * Segment mode (long lines): the pipelined segment pass with every segment inside one region
+ * (rt_regions_plan_segments), each taking its region's cell map; admissible when 16 divides
+ * every region's first cell and N.  The steps always run the pipelined schedule (as under
+ * rt_set_pipeline(2)), in time blocks of 1..8, 10, 12 or 16 steps; a run's remainder below the
+ * time block runs as at most two further pipelined runs of smaller blocks.  The results do not
+ * depend on the time block, the segmentation or how a run is cut into rt_advance calls,
+ * bitwise, and equal chain mode's bitwise. */
 typedef struct {
   int cells;                 /* > 0 */
   double width;              /* > 0; the region's dx = width / cells */
@@ -433,6 +447,17 @@ rt_status rt_regions_plan(const rt_region *r, int nregions, int reflective, int 
  * per lane wherever the tick table says so). */
 rt_status rt_regions_plan_steps(const rt_region *r, int nregions, int reflective, int max_waves, long long nsteps,
                                 int *cells_per_lane, int *waves, int *lanes);
+/* Host only, valid without a GPU.  The segments a region handle in segment mode cuts its
+ * lines into: N and every region's first cell must be multiples of 16 (else RT_ERR_PARAM, as
+ * for cells <= 0 or width <= 0).  target_cells is rounded up to a multiple of 16, at least 16.
+ * A region of n cells becomes k = ceil(n / target) segments, each a multiple of 16 cells, the
+ * region's n / 16 units dealt out as evenly as possible with the longer segments first (272
+ * cells at target 64: 64, 64, 48, 48, 48).  *segments = Sg; first_cell[0 .. Sg] and
+ * segment_region[0 .. Sg - 1] (Sg <= N / 16; call with both NULL for Sg alone) in physical
+ * cells, left to right: the mu > 0 lines sweep them as they are, the mu < 0 lines their mirror
+ * image (upwind segment s covers N - first_cell[Sg - s] .. N - first_cell[Sg - 1 - s] - 1). */
+rt_status rt_regions_plan_segments(const rt_region *r, int nregions, int target_cells, int *segments,
+                                   int *first_cell, int *segment_region);
 /* The regions of a .prm with have_regions (num_regions, filename_regions: a table of
  * num_regions x 5 values, one row `cells width rho kappa_grey T` per region, read from
  * table_dir as the group tables are).  With have_group_absorption_opacities every region's
@@ -449,14 +474,27 @@ void rt_regions_free(rt_region *r);
  * (B_g, dB/dT_g, the correction constants; include_validation validates each), and every cell
  * starts at its own region's B_g.  Stepping, rt_set_ends, group shards and the state's
  * read-outs work as on any handle; the balance terms and rt_group_absorption_device use each
- * cell's own rho kappa_g, dx and emission.  RT_ERR_PARAM: use_mg_equilib, or a layout with
- * no admissible chain.  RT_ERR_STATE on a region handle: rt_material_enable (material
- * coupling is rt_material_enable_regions, one heat capacity per region),
- * rt_set_time_block, rt_set_pipeline, rt_set_segmentation, rt_set_level_waves,
- * rt_set_wavefront(0), rt_plan_schedule.  rt_set_wavefront_cells with a C that is not
- * admissible falls back to the plan's; rt_set_wavefront_waves re-plans (RT_ERR_PARAM, nothing
- * changed, when no chain fits any more).  rt_get_group_data returns region 0's B, dBdT and
- * kappa. */
+ * cell's own rho kappa_g, dx and emission.  RT_ERR_PARAM: use_mg_equilib, or a layout
+ * admissible neither for a chain nor for segments (N = 513 cut at 5).  A layout with no
+ * admissible chain that is admissible for segments starts in segment mode;
+ * rt_set_wavefront(s, 0) on a chain-mode handle whose layout is admissible for segments enters
+ * it (with nothing queued and no material coupling, else RT_ERR_STATE), and
+ * rt_set_wavefront(s, 1 or 2) goes back to the chain where one fits (else RT_ERR_STATE) after
+ * draining the pipeline.  rt_get_wavefront reports active = 0 in segment mode.
+ * RT_ERR_STATE on every region handle: rt_material_enable (material coupling is
+ * rt_material_enable_regions, one heat capacity per region), rt_set_level_waves,
+ * rt_plan_schedule.
+ * RT_ERR_STATE in chain mode: rt_set_time_block, rt_set_pipeline, rt_set_segmentation, and
+ * rt_set_wavefront(0) where the layout is not admissible for segments.
+ * RT_ERR_STATE in segment mode: rt_set_pipeline(0) (1 and 2 both mean the pipelined
+ * schedule), rt_set_time_block beyond 16, rt_material_enable_regions (the coupled pass is an
+ * aligned pass).  rt_set_time_block (1..8, 10, 12, 16; default 16) and rt_set_segmentation
+ * work: the workgroups-per-CU target gives the cells per segment a uniform line would get,
+ * which is rt_regions_plan_segments' target_cells; rt_sweep_geometry reports the planned
+ * segments.  rt_set_map_form never selects the lean maps on a region handle.
+ * rt_set_wavefront_cells with a C that is not admissible falls back to the plan's;
+ * rt_set_wavefront_waves re-plans (RT_ERR_PARAM, nothing changed, when no chain fits any
+ * more).  rt_get_group_data returns region 0's B, dBdT and kappa. */
 rt_status rt_create_regions(const rt_params *p, const rt_region *r, int nregions, int g_lo, int g_hi, int device,
                             rt_solver **out);
 /* *nregions (1 for a handle without regions) and first_cell[0 .. nregions]: region k holds the

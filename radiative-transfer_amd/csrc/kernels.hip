@@ -278,8 +278,13 @@ __device__ __forceinline__ void group_sums(const double (&vals)[C], double w, in
 // levels, each one pass behind its upwind neighbour, so every segment starts
 // from the exact incoming state that neighbour published in the previous
 // launch -- no provisional state, no correction.
-template <int S, int T, int MODE, bool CB = false>
+// REG (MODE 2 only): a slab of regions on long lines -- every segment lies inside one region,
+// so the pass is the same with per-segment bounds (seg_first) and the segment's region's map
+// (seg_region picks the row block of map); both are workgroup-uniform.  The carried state is
+// the physical interface state and crosses region edges between segments untransformed.
+template <int S, int T, int MODE, bool CB = false, bool REG = false>
 __global__ __launch_bounds__(64) void sweep_block_kernel(SegArgs a) {
+  static_assert(!REG || (MODE == 2 && !CB), "the region form is the pipelined pass");
   constexpr int K = SchemeDim<S>::K;
   constexpr int KC = T * K;
   constexpr int WN = map_count<S>();
@@ -314,8 +319,15 @@ __global__ __launch_bounds__(64) void sweep_block_kernel(SegArgs a) {
   }
   const int ell = q * 64 + lane;
   const bool neg = half == 0;
-  const int k_begin = s * a.Ls;
-  const int k_end = min(a.N, k_begin + a.Ls);
+  int k_begin, k_end;
+  if constexpr (REG) {  // the planner's segments, in this half's upwind numbering
+    const int *sf = a.seg_first + half * (a.Sg + 1) + s;
+    k_begin = sf[0];
+    k_end = min(a.N, sf[1]);
+  } else {
+    k_begin = s * a.Ls;
+    k_end = min(a.N, k_begin + a.Ls);
+  }
   if (k_begin >= k_end) return;
   if (MODE == 1 && s == 0) return;  // segment 0 is never provisional
   const size_t seg_stride = static_cast<size_t>(KC) * stride;
@@ -439,8 +451,14 @@ __global__ __launch_bounds__(64) void sweep_block_kernel(SegArgs a) {
 
   // ---- the line's cell map ----
   double W[WN];
+  if constexpr (REG) {  // the segment's region's rows of [nregions][2][WN][Lpad]
+    const double *mp = a.map + (static_cast<size_t>(a.seg_region[half * a.Sg + s]) * 2 + half) * WN * stride + ell;
 #pragma unroll
-  for (int n = 0; n < WN; ++n) W[n] = a.map[(static_cast<size_t>(half) * WN + n) * stride + ell];
+    for (int n = 0; n < WN; ++n) W[n] = mp[n * stride];
+  } else {
+#pragma unroll
+    for (int n = 0; n < WN; ++n) W[n] = a.map[(static_cast<size_t>(half) * WN + n) * stride + ell];
+  }
 
   int k0 = k_begin;
   for (; k0 + C < k_end; k0 += C) {  // full chunks with a successor
@@ -1762,8 +1780,17 @@ static hipError_t launch_t(int mode, const SegArgs &a, int grid, hipStream_t st)
     if (mode != SWEEP_FINALIZE) return hipErrorInvalidValue;  // the correction has no source term
   }
   if (mode == SWEEP_PIPELINED) {
+    if (a.seg_first && a.level_waves != 1) return hipErrorInvalidValue;  // no level-split region form
     if (a.level_waves != 1) {  // level-split pass (kernels_split.hip)
       if constexpr (level_split_supported(S, T)) return launch_split(T, a.level_waves, a, grid, st);
+      return hipErrorInvalidValue;
+    }
+    if (a.seg_first) {  // a slab of regions: the region form, T in {1..8, 10, 12, 16}
+      if constexpr (region_block(T)) {
+        if (!a.seg_region) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((sweep_block_kernel<S, T, 2, false, true>), dim3(grid), dim3(64), 0, st, a);
+        return hipGetLastError();
+      }
       return hipErrorInvalidValue;
     }
     if constexpr (one_wave_block(S, T)) {

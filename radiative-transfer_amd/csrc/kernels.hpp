@@ -21,6 +21,8 @@ constexpr bool level_split_supported(int S, int T) {
 // pipelined passes with a one-wave kernel: all but BDF2 beyond 20 levels (its carried
 // states would spill; those run split over four waves)
 constexpr bool one_wave_block(int S, int T) { return S != 3 || T <= 20; }
+// time blocks of the region form of the one-wave pipelined pass (a region handle in segment mode)
+constexpr bool region_block(int T) { return (T >= 1 && T <= 8) || T == 10 || T == 12 || T == 16; }
 // rows per chunk of the level-split pass (16 rows with T/2 = 8 levels spill past 256 registers)
 constexpr int split_chunk_cells() { return 8; }
 constexpr int kXcds = 8;                                // gfx950: workgroups are dealt to 8 XCDs round-robin
@@ -69,6 +71,13 @@ struct SegArgs {
   // has no psi term, [lean_map_rows()][Lpad]: the mu < 0 lines' packed rows, then the mu > 0
   // lines' (cell.hpp, lean_pattern)
   const double *lmap;         // nullptr: the full map
+  // multi-region slabs on long lines (the REG form of the one-wave pipelined pass): every
+  // segment lies in one region.  seg_first[half][Sg + 1]: first cell of segment s (and the end
+  // of the last) in the half's upwind numbering; seg_region[half][Sg]: its region, the row
+  // block of map ([nregions][2][map_count<S>][Lpad]) the segment's cells take.  hmap stays
+  // region 0's (the reflective head cell is physical cell 0)
+  const int *seg_first;       // nullptr: one medium, segments s * Ls
+  const int *seg_region;
 };
 
 struct FoldArgs {

@@ -76,6 +76,57 @@ std::vector<int> lane_table(const std::vector<int> &first_cell, int C) {
   return out;
 }
 
+bool segments_admissible(const std::vector<int> &first_cell) {
+  if (first_cell.size() < 2 || first_cell.back() < 1) return false;
+  for (int f : first_cell)
+    if (f % kSegmentUnit) return false;
+  return true;
+}
+
+int segment_target(long long target_cells) {
+  if (target_cells < kSegmentUnit) return kSegmentUnit;
+  if (target_cells > 2147483647LL - kSegmentUnit) target_cells = 2147483647LL - kSegmentUnit;
+  return static_cast<int>((target_cells + kSegmentUnit - 1) / kSegmentUnit * kSegmentUnit);
+}
+
+int plan_segments(const std::vector<int> &first_cell, long long target_cells, std::vector<int> &seg_first,
+                  std::vector<int> &seg_region) {
+  seg_first.clear();
+  seg_region.clear();
+  if (!segments_admissible(first_cell)) return 0;
+  const int target = segment_target(target_cells);
+  seg_first.push_back(0);
+  for (size_t r = 0; r + 1 < first_cell.size(); ++r) {
+    const int n = first_cell[r + 1] - first_cell[r], units = n / kSegmentUnit;
+    const int k = (n - 1) / target + 1;  // ceil(n / target) <= units
+    const int base = units / k, longer = units % k;
+    int at = first_cell[r];
+    for (int j = 0; j < k; ++j) {
+      at += (base + (j < longer ? 1 : 0)) * kSegmentUnit;
+      seg_first.push_back(at);
+      seg_region.push_back(static_cast<int>(r));
+    }
+  }
+  return static_cast<int>(seg_region.size());
+}
+
+std::vector<int> segment_tables(const std::vector<int> &seg_first, const std::vector<int> &seg_region) {
+  const size_t Sg = seg_region.size();
+  std::vector<int> out(2 * (Sg + 1) + 2 * Sg);
+  if (!Sg || seg_first.size() != Sg + 1) return std::vector<int>();
+  const int N = seg_first.back();
+  int *first0 = out.data(), *first1 = first0 + Sg + 1, *reg0 = first1 + Sg + 1, *reg1 = reg0 + Sg;
+  for (size_t s = 0; s <= Sg; ++s) {
+    first0[s] = N - seg_first[Sg - s];
+    first1[s] = seg_first[s];
+  }
+  for (size_t s = 0; s < Sg; ++s) {
+    reg0[s] = seg_region[Sg - 1 - s];
+    reg1[s] = seg_region[s];
+  }
+  return out;
+}
+
 }  // namespace rtamd::regions
 
 // ---------------------------------------------------------------------------
@@ -115,6 +166,22 @@ extern "C" rt_status rt_regions_plan_steps(const rt_region *r, int nregions, int
     return rfail(RT_ERR_PARAM, "regions: no chain of 1, 2, 4 or 8 cells per lane both divides every region edge "
                                "and fits the waves (N <= 512 at C = 1, 256 reflective; edges on multiples of 8 "
                                "allow 4096, 2048 reflective)");
+  return RT_OK;
+}
+
+extern "C" rt_status rt_regions_plan_segments(const rt_region *r, int nregions, int target_cells, int *segments,
+                                              int *first_cell, int *segment_region) {
+  if (!r || nregions < 1) return rfail(RT_ERR_ARG, "rt_regions_plan_segments: NULL regions or nregions < 1");
+  if (segments) *segments = 0;
+  std::vector<int> fc, sf, sr;
+  if (!rtamd::regions::first_cells(r, nregions, fc))
+    return rfail(RT_ERR_PARAM, "regions: every region needs cells > 0 and width > 0");
+  const int Sg = rtamd::regions::plan_segments(fc, target_cells, sf, sr);
+  if (!Sg)
+    return rfail(RT_ERR_PARAM, "regions: segments need N and every region's first cell on multiples of 16");
+  if (segments) *segments = Sg;
+  if (first_cell) std::memcpy(first_cell, sf.data(), sizeof(int) * sf.size());
+  if (segment_region) std::memcpy(segment_region, sr.data(), sizeof(int) * sr.size());
   return RT_OK;
 }
 

@@ -1,6 +1,7 @@
 // regions.hpp -- host logic of the multi-region slabs (include/rtsn.h rt_regions_*,
 // rt_create_regions): which chain a slab of piecewise-constant regions takes, the per-lane and
-// per-cell region tables the kernels index, and the .prm's region table.  Plain C++, no HIP:
+// per-cell region tables the kernels index, the segments of a long line (plan_segments), and
+// the .prm's region table.  Plain C++, no HIP:
 // built into librtsn with the host objects and alone (tools/regions_sanitize.cpp).
 //
 // A chain lane of the short-line wavefront (kernels_wave.hip) holds C consecutive cells and one
@@ -33,5 +34,22 @@ std::vector<int> cell_table(const std::vector<int> &first_cell);
 // lane_region[half][lanes] at C cells per lane: half 1 (mu > 0) lane j holds the physical
 // cells [j C, (j + 1) C), half 0 (mu < 0) lane j the cells N - 1 - (j C + c): the mirror image
 std::vector<int> lane_table(const std::vector<int> &first_cell, int C);
+
+// Long lines (the region form of the pipelined segment pass, kernels.hip): a segment holds one
+// cell map, so it must lie in one region, and its length is a multiple of the 16-cell register
+// tile -- admissible when 16 divides every region's first cell and N.
+constexpr int kSegmentUnit = 16;
+bool segments_admissible(const std::vector<int> &first_cell);
+// target_cells rounded up to a multiple of 16, at least 16
+int segment_target(long long target_cells);
+// The cutting rule: a region of n cells becomes k = ceil(n / target) segments, its n / 16 units
+// dealt out as evenly as possible, the longer segments first.  seg_first[0 .. Sg] (physical
+// cells, left to right) and seg_region[0 .. Sg - 1]; returns Sg (0: not admissible)
+int plan_segments(const std::vector<int> &first_cell, long long target_cells, std::vector<int> &seg_first,
+                  std::vector<int> &seg_region);
+// The kernel's tables in each half's upwind numbering: [2][Sg + 1] first cells, then [2][Sg]
+// regions; half 1 (mu > 0) as planned, half 0 (mu < 0) the mirror image: upwind segment s
+// covers the physical cells N - seg_first[Sg - s] .. N - seg_first[Sg - 1 - s] - 1
+std::vector<int> segment_tables(const std::vector<int> &seg_first, const std::vector<int> &seg_region);
 
 }  // namespace rtamd::regions

@@ -255,6 +255,7 @@ static rt_status create_impl(const rt_params *pin, int g_lo, int g_hi, int d_lo,
   if (e) return fail(nullptr, RT_ERR_NOMEM, std::string("device allocation: ") + hipGetErrorString(e));
 
   h->tau.assign(chain_positions(h), 0);
+  if (h->seg_mode && (st = upload_segment_tables(h))) return st;  // the plan segment_lines made above
   if ((st = setup_lines(h))) return st;
   if ((st = upload_inflow(h))) return st;
   HIP_TRY(h, launch_init_state(static_cast<double2 *>(h->E.p), static_cast<const double *>(h->lineB.p), geometry(h),
@@ -283,7 +284,12 @@ extern "C" rt_status rt_set_pipeline(rt_solver *s, int on) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_pipeline: NULL handle");
   HIP_TRY(s, hipSetDevice(s->device));
   if (on < 0 || on > 2) return fail(s, RT_ERR_ARG, "rt_set_pipeline: 0 (off), 1 (auto) or 2 (always)");
-  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_pipeline: a region handle always runs the wavefront");
+  if (regional(s)) {
+    if (!s->seg_mode) return fail(s, RT_ERR_STATE, "rt_set_pipeline: a region handle in chain mode runs the wavefront");
+    if (!on) return fail(s, RT_ERR_STATE, "rt_set_pipeline: a region handle in segment mode always runs the pipelined schedule");
+    s->pipe_set = true;  // 1 and 2 mean the same: always pipelined
+    return RT_OK;
+  }
   if (!on && s->pipe) {
     if (rt_status st = complete(s)) return st;  // leave the positions aligned
   }
@@ -296,7 +302,27 @@ extern "C" rt_status rt_set_pipeline(rt_solver *s, int on) {
 extern "C" rt_status rt_set_wavefront(rt_solver *s, int mode) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_wavefront: NULL handle");
   if (mode < 0 || mode > 2) return fail(s, RT_ERR_ARG, "rt_set_wavefront: 0 (off), 1 (auto) or 2 (on)");
-  if (regional(s) && mode == 0) return fail(s, RT_ERR_STATE, "rt_set_wavefront: a region handle always runs the wavefront");
+  if (regional(s) && mode == 0) {  // chain mode -> segment mode, where the layout admits segments
+    if (s->seg_mode) return RT_OK;
+    if (!regions::segments_admissible(s->first_cell))
+      return fail(s, RT_ERR_STATE, "rt_set_wavefront: this region handle runs the wavefront only (segments need N and "
+                                   "every region's first cell on multiples of 16)");
+    if (s->material)
+      return fail(s, RT_ERR_STATE, "rt_set_wavefront: material coupling is on, and segment mode has no coupled pass");
+    if (s->wqueued || s->queued)
+      return fail(s, RT_ERR_STATE, "rt_set_wavefront: steps are queued; read the state out or rt_finish first");
+    HIP_TRY(s, hipSetDevice(s->device));
+    return enter_segment_mode(s);
+  }
+  if (regional(s) && s->seg_mode) {  // segment mode -> chain mode, where a chain fits
+    if (!region_wave_plan(s, s->wave_max).C)
+      return fail(s, RT_ERR_STATE, "rt_set_wavefront: no chain fits this region handle's lines (segment mode only)");
+    HIP_TRY(s, hipSetDevice(s->device));
+    if (rt_status st = complete(s)) return st;  // drain: every position at the requested time
+    leave_segment_mode(s);
+    s->wave = mode;
+    return RT_OK;
+  }
   if (s->wqueued) {  // steps queued for the current chain plan run on it first
     HIP_TRY(s, hipSetDevice(s->device));
     if (rt_status st = wave_flush(s)) return st;
@@ -364,7 +390,10 @@ extern "C" rt_status rt_set_time_block(rt_solver *s, int steps_per_pass) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_time_block: NULL handle");
   if (!supported_time_block(steps_per_pass))
     return fail(s, RT_ERR_ARG, "rt_set_time_block: steps per pass must be 1..8, 10, 12, 16, 20, 24, 32 or 40");
-  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_time_block: a region handle always runs the wavefront");
+  if (regional(s) && !s->seg_mode)
+    return fail(s, RT_ERR_STATE, "rt_set_time_block: a region handle in chain mode runs the wavefront");
+  if (regional(s) && !region_block(steps_per_pass))
+    return fail(s, RT_ERR_STATE, "rt_set_time_block: a region handle in segment mode takes 1..8, 10, 12 or 16 steps per pass");
   HIP_TRY(s, hipSetDevice(s->device));
   s->T = steps_per_pass;
   s->T_set = true;
@@ -381,7 +410,7 @@ extern "C" rt_status rt_get_time_block(rt_solver *s, int *steps_per_pass) {
 extern "C" rt_status rt_set_level_waves(rt_solver *s, int waves) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_level_waves: NULL handle");
   if (waves < 0 || waves > 4 || waves == 3) return fail(s, RT_ERR_PARAM, "rt_set_level_waves: 0 (auto), 1, 2 or 4");
-  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_level_waves: a region handle always runs the wavefront");
+  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_level_waves: a region handle has no level-split pass");
   HIP_TRY(s, hipSetDevice(s->device));
   s->level_waves = waves;  // segments re-sized for its occupancy before the next pass (the schedule is exact
   s->lw_set = true;        // for any segmentation)
@@ -393,7 +422,8 @@ extern "C" rt_status rt_set_level_waves(rt_solver *s, int waves) {
 extern "C" rt_status rt_set_segmentation(rt_solver *s, int wgs_per_cu) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_segmentation: NULL handle");
   if (wgs_per_cu < 0 || wgs_per_cu > 64) return fail(s, RT_ERR_ARG, "rt_set_segmentation: 0 (occupancy) .. 64");
-  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_set_segmentation: a region handle always runs the wavefront");
+  if (regional(s) && !s->seg_mode)
+    return fail(s, RT_ERR_STATE, "rt_set_segmentation: a region handle in chain mode runs the wavefront");
   HIP_TRY(s, hipSetDevice(s->device));
   s->seg_wgs = wgs_per_cu;
   s->seg_set = true;
@@ -440,6 +470,16 @@ extern "C" rt_status rt_debug_fail_launch(rt_solver *s, int after) {
   if (after < -1) return fail(s, RT_ERR_ARG, "rt_debug_fail_launch: -1 (off) or launches before the failure");
   s->fail_launch_after = after;
   return RT_OK;
+}
+
+extern "C" rt_status rt_debug_set_segment_cells(rt_solver *s, int cells) {
+  if (!s) return fail(nullptr, RT_ERR_ARG, "rt_debug_set_segment_cells: NULL handle");
+  if (cells < 0) return fail(s, RT_ERR_ARG, "rt_debug_set_segment_cells: 0 (the segmentation's target) or cells per segment");
+  if (!s->seg_mode) return fail(s, RT_ERR_STATE, "rt_debug_set_segment_cells: not a region handle in segment mode");
+  HIP_TRY(s, hipSetDevice(s->device));
+  s->seg_cells_dbg = cells;
+  s->seg_T = 0;  // planned again: now if the positions are aligned, else before the next pipeline starts
+  return resegment(s);
 }
 
 extern "C" rt_status rt_debug_set_transfer_chunk(rt_solver *s, long long doubles) {

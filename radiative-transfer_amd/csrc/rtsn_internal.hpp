@@ -260,8 +260,8 @@ struct rt_solver {
   rtsn_detail::DeviceBuf corr_rows;           // BDF2: rows b A^j and A^64 per line (phi_correction_rows_kernel)
   bool phi_fused = false;        // angular sums fused into the coupled pass (M/2 divides 64)
   PlanckCells pc{};
-  // a slab of regions (rt_create_regions, rtsn_regions.hip): the handle then always runs the
-  // wavefront, with `map` holding one map set per region.  p.X is the regions' total width and
+  // a slab of regions (rt_create_regions, rtsn_regions.hip): the handle then runs the wavefront
+  // (chain mode) or the pipelined segment pass (seg_mode), with `map` holding one map set per region.  p.X is the regions' total width and
   // p.rho, p.kappa_grey, p.T, gt are region 0's
   struct Region {
     rt_params p{};               // the handle's parameters with this region's rho, kappa_grey, T, group_kappa
@@ -279,6 +279,14 @@ struct rt_solver {
   rtsn_detail::DeviceBuf rmaterial;
   std::vector<double> rho_cv_r;  // [regions] heat capacities (host copy: rt_material_stability)
   long long lane_off[4] = {-1, -1, -1, -1};
+  // segment mode (long lines): the pipelined segment pass with every segment inside one region
+  // (regions::plan_segments at the target Ls of segment_lines); seg_tab the kernel's tables
+  // (regions::segment_tables: [2][Sg + 1] first cells, then [2][Sg] regions), allocated for the
+  // most segments a line can have (N / 16)
+  bool seg_mode = false;
+  int seg_cells_dbg = 0;                   // test hook (rt_debug_set_segment_cells): the planner's target, 0 the segmentation's
+  std::vector<int> seg_first, seg_region;  // the plan in physical cells: [Sg + 1], [Sg]
+  rtsn_detail::DeviceBuf seg_tab;
   // profiling
   bool profiling = false;
   std::vector<hipEvent_t> ev_pool;   // (start, stop) pairs of profiled launches
@@ -334,6 +342,7 @@ inline bool lean_maps(const rt_solver *s) {
 // needs 126 AGPRs beside 256 VGPRs (9% extra moves; split 8.29-8.31 vs 8.52-8.53 ms/step
 // on SL, profiles/archive/r02b_split20.jsonl) -- and one wave otherwise (T = 16: 4% faster).
 inline int level_waves_of(const rt_solver *s, int T) {
+  if (!s->regions.empty()) return 1;  // a region handle's segment pass is the one-wave kernel's region form
   if (s->scheme != SCHEME_BDF2 || !split_block(T)) return 1;  // the split kernel is BDF2's
   if (T > 20) return 4;                                         // one or two waves would spill
   int lw = s->level_waves ? s->level_waves : (T == 20 ? 2 : 1);
@@ -354,6 +363,7 @@ inline int level_waves_of(const rt_solver *s, int T) {
 // profiles/archive/r03ar_trace_summary.json).  Ties go to the most waves within that count.
 inline int fill_level_waves(const rt_solver *s, int grid) {
   const int base = level_waves_of(s, s->Tpipe);
+  if (!s->regions.empty()) return base;
   if (s->level_waves || s->scheme != SCHEME_BDF2 || !split_block(s->Tpipe)) return base;
   const int T = s->Tpipe;
   const long long full = 2LL * s->Q * s->Sg * base;  // waves of a launch with every position active
@@ -376,6 +386,7 @@ inline int fill_level_waves(const rt_solver *s, int grid) {
 // outflow), other schemes, blocks without a tail kernel.  complete() takes a tail of at
 // least T / waves steps, so that wave 0 (which streams the rows in) runs the plain body.
 inline int tail_waves(const rt_solver *s, int T) {
+  if (!s->regions.empty()) return 0;  // no region form of the tail kernels
   if (s->scheme != SCHEME_BDF2 || s->p.bc_left_indicator == 2) return 0;
   for (int k : {4, 2})
     if (split_tail_supported(T, k)) return k;
@@ -459,6 +470,11 @@ inline bool regional(const rt_solver *s) { return !s->regions.empty(); }
 rt_status setup_regions(rt_solver *s, const rt_region *r, int nregions);  // create: before the group table
 rt_status upload_regions(rt_solver *s);                                   // create: maps, tables, initial state
 WavePlan region_wave_plan(const rt_solver *s, int wave_max);
+// segment mode (a region handle on the pipelined segment pass): enter it (aligned positions,
+// nothing queued), leave it for the chain, and the kernel's tables for the current plan
+rt_status enter_segment_mode(rt_solver *s);
+void leave_segment_mode(rt_solver *s);
+rt_status upload_segment_tables(rt_solver *s);
 // the region forms of line_maps_s (one map set per region into s->map, region 0's head map)
 template <int S>
 rt_status region_maps_s(rt_solver *s, bool unit_B = false);  // unit_B: into map_unit, hmap_unit

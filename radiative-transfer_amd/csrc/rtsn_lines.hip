@@ -375,6 +375,12 @@ void rtsn_detail::segment_lines(rt_solver *h, int waves_per_cu, long long max_sg
   ls = ((ls + kSweepCells - 1) / kSweepCells) * kSweepCells;
   h->Ls = static_cast<int>(ls);
   h->Sg = static_cast<int>((h->p.N + ls - 1) / ls);
+  // a region handle in segment mode: the Ls a uniform line would get is the planner's target,
+  // and every segment lies in one region (Ls stays the target: the region form reads seg_first)
+  if (h->seg_mode) {
+    if (h->seg_cells_dbg) h->Ls = regions::segment_target(h->seg_cells_dbg);
+    h->Sg = regions::plan_segments(h->first_cell, h->Ls, h->seg_first, h->seg_region);
+  }
 }
 
 // Segments of an aligned pass.  The pass sweeps every segment at once (Ls cells x Ta
@@ -438,6 +444,8 @@ rt_status rtsn_detail::resegment(rt_solver *h, bool aligned) {
   if (h->Sg == sg0 && h->Ls == ls0) return RT_OK;
   if (2LL * h->Q * h->Sg >= (1LL << 31)) return fail(h, RT_ERR_PARAM, "too many lines for one handle: shard the groups");
   HIP_TRY(h, alloc_segments(h));
+  if (h->seg_mode)
+    if (rt_status st = upload_segment_tables(h)) return st;
   h->tau.assign(chain_positions(h), h->target);  // every position at the same, requested time
   h->resume_lo = h->resume_hi = -1;
   return RT_OK;

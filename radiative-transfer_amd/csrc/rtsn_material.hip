@@ -107,6 +107,9 @@ extern "C" rt_status rt_material_enable_regions(rt_solver *s, const double *rho_
     if (!(rho_cv[k] > 0.0) || !std::isfinite(rho_cv[k]))
       return fail(s, RT_ERR_ARG, "rt_material_enable_regions: every rho_cv must be > 0");
   if (!regional(s)) return rt_material_enable(s, rho_cv[0], T_cells);
+  if (s->seg_mode)
+    return fail(s, RT_ERR_STATE, "rt_material_enable_regions: the handle is in segment mode, which has no coupled pass "
+                                 "(the coupled step runs on the wavefront chain)");
   if (s->p.use_correction && s->p.V != 0.0)
     return fail(s, RT_ERR_PARAM, "material coupling needs the v/c correction off (V = 0 or use_correction = 0)");
   HIP_TRY(s, hipSetDevice(s->device));

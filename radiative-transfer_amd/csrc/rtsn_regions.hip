@@ -1,6 +1,7 @@
 // rtsn_regions.hip -- the device side of a region handle (include/rtsn.h "multi-region
 // slabs"; the host logic is regions.cpp): per-region group tables, the lane -> region and
-// cell -> region tables the kernels index, the initial state, and the region getters.
+// cell -> region tables the kernels index, the initial state, the region getters, and the
+// change between chain mode and segment mode (the segment plan's tables).
 // rt_create_regions itself sits with the other constructors in rtsn_api.hip; the per-region
 // cell maps are built in rtsn_lines.hip (region_maps_s).
 
@@ -27,11 +28,56 @@ rt_status rtsn_detail::setup_regions(rt_solver *s, const rt_region *r, int nregi
     if (rt_status st = phys::build_group_table(g.p, g.gt))
       return fail(s, st, "group table: group edges must increase");
   }
-  s->wave = 2;  // the wavefront, always
-  if (!region_wave_plan(s, s->wave_max).C)
-    return fail(s, RT_ERR_PARAM, "regions: no chain of 1, 2, 4 or 8 cells per lane both divides every region edge "
-                                 "and fits 8 waves");
+  s->wave = 2;  // the wavefront where a chain fits
+  if (!region_wave_plan(s, s->wave_max).C) {
+    if (!regions::segments_admissible(s->first_cell))
+      return fail(s, RT_ERR_PARAM, "regions: no chain of 1, 2, 4 or 8 cells per lane both divides every region edge "
+                                   "and fits 8 waves, and the region edges are not multiples of 16 (segments)");
+    s->seg_mode = true;  // long lines: the pipelined segment pass (create plans the segments)
+    s->wave = 0;
+    s->pipe = 2;
+  }
   return RT_OK;
+}
+
+// Chain mode -> segment mode: the caller has checked the layout, that nothing is queued and
+// that no material coupling is on.  The stored state is exact and every position at the same
+// time; the segments are planned for the current time block (resegment).
+rt_status rtsn_detail::enter_segment_mode(rt_solver *s) {
+  if (s->seg_mode) return RT_OK;
+  const int T0 = s->T;
+  if (!region_block(s->T)) s->T = default_time_block(s->scheme);
+  s->seg_mode = true;
+  s->Sg = 0;  // no plan yet: resegment allocates for the planner's segments and uploads the tables
+  s->seg_T = 0;
+  if (rt_status st = resegment(s)) {
+    s->seg_mode = false;
+    s->T = T0;
+    s->seg_T = 0;  // (the uniform segmentation is never used by the chain)
+    s->Sg = 1;
+    return st;
+  }
+  s->wave = 0;
+  s->pipe = 2;
+  return RT_OK;
+}
+
+void rtsn_detail::leave_segment_mode(rt_solver *s) {  // drained (complete) by the caller
+  s->seg_mode = false;
+  s->pipe = 1;
+  s->pipe_set = false;
+}
+
+rt_status rtsn_detail::upload_segment_tables(rt_solver *s) {
+  const std::vector<int> t = regions::segment_tables(s->seg_first, s->seg_region);
+  if (t.empty() || static_cast<int>(s->seg_region.size()) != s->Sg)
+    return fail(s, RT_ERR_STATE, "regions: no segment plan");
+  if (!s->seg_tab.p) {
+    const size_t most = static_cast<size_t>(s->p.N) / regions::kSegmentUnit;
+    if (dalloc(s->seg_tab, sizeof(int) * (4 * most + 2)) != hipSuccess)
+      return fail(s, RT_ERR_NOMEM, "device allocation: segment tables");
+  }
+  return upload(s, s->seg_tab, t.data(), sizeof(int) * t.size());
 }
 
 WavePlan rtsn_detail::region_wave_plan(const rt_solver *s, int wave_max) {

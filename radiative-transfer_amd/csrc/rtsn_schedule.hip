@@ -61,6 +61,10 @@ SegArgs rtsn_detail::seg_args(rt_solver *s) {
   a.pending = s->pending ? 1 : 0;
   a.hd = 0.5 * (s->p.X / s->p.N);
   a.level_waves = level_waves_of(s, s->T);
+  if (s->seg_mode) {  // every segment in one region: the region form of the pipelined pass
+    a.seg_first = static_cast<const int *>(s->seg_tab.p);
+    a.seg_region = a.seg_first + 2 * (s->Sg + 1);
+  }
   return a;
 }
 
@@ -129,6 +133,7 @@ static rt_status event_end(rt_solver *s, hipEvent_t e1) {
 // One pass of T full steps, every segment at the same time level.
 // coupled: the material-coupled sweep (T = 1, per-cell emission).
 rt_status rtsn_detail::enqueue_pass(rt_solver *s, int T, bool coupled) {
+  if (s->seg_mode) return fail(s, RT_ERR_STATE, "regions: segment mode has no aligned pass");
   if (rt_status st = ensure_segments(s)) return st;
   if (s->pending && s->Tp != T) {
     rt_status st = apply_correction(s);
@@ -170,6 +175,7 @@ rt_status rtsn_detail::enqueue_pass(rt_solver *s, int T, bool coupled) {
 
 // nsteps full steps in aligned passes of at most T (and kMaxAlignedBlock) steps.
 static rt_status enqueue_steps(rt_solver *s, int nsteps) {
+  if (s->seg_mode) return fail(s, RT_ERR_STATE, "regions: segment mode has no aligned pass");
   if (rt_status st = resegment(s, true)) return st;
   const int T = std::min(s->T, kMaxAlignedBlock);
   while (nsteps > 0) {
@@ -209,6 +215,7 @@ static rt_status enqueue_steps(rt_solver *s, int nsteps) {
 // full launch (k = P), a caller-set level split and other schemes keep one launch.
 static int ramp_chunk(const rt_solver *s, int k, int grid_per_pos) {
   const int T = s->Tpipe, P = chain_positions(s);
+  if (regional(s)) return k;  // one-wave launches: nothing to gain from a cut
   if (k >= P || s->level_waves || s->scheme != SCHEME_BDF2 || !split_block(T) || T % 4) return k;
   int wpc = 0;
   if (split_occupancy(T, 4, &wpc) != hipSuccess || wpc < 1) return k;
@@ -348,6 +355,27 @@ static rt_status pipe_advance(rt_solver *s, int nsteps) {
   return RT_OK;
 }
 
+// Segment mode (a region handle on long lines) has no aligned pass: the queued remainder
+// r < T runs as further pipelined runs of smaller blocks, largest first (15 = 12 + 3,
+// 9 = 8 + 1: at most two for T <= 16), each filling and draining on the current segments.  A
+// failed launch leaves the run's pipeline (Tpipe) and the rest of the remainder queued; the
+// next call drains the one and runs the other.
+static rt_status segment_remainder(rt_solver *s) {
+  if (rt_status st = resegment(s)) return st;
+  while (s->queued) {
+    int b = std::min(s->queued, 12);
+    while (!region_block(b)) --b;
+    s->queued -= b;
+    s->Tpipe = b;
+    s->pipe_base = s->tau[0];
+    s->target += b;
+    while (s->tau.back() < s->target)
+      if (rt_status st = pipe_launch(s)) return st;
+    s->Tpipe = 0;
+  }
+  return RT_OK;
+}
+
 // Bring every position to the target (drain) and run the queued remainder.  A planned
 // schedule ends with its run's pipeline.
 rt_status rtsn_detail::complete(rt_solver *s) {
@@ -368,6 +396,7 @@ rt_status rtsn_detail::complete(rt_solver *s) {
     s->Tpipe = 0;
   }
   end_plan(s);
+  if (s->queued && s->seg_mode) return segment_remainder(s);
   if (s->queued) {
     const int r = s->queued;
     s->queued = 0;
@@ -405,7 +434,7 @@ WavePlan rtsn_detail::wave_plan(const rt_solver *s) {
 // SIMDs, and the segment pipeline's full-chip passes (28 FMAs per cell and level at ~90% of
 // the FP64 issue rate) carry the same work with less overhead per cell.
 bool rtsn_detail::use_wavefront(const rt_solver *s) {
-  if (regional(s)) return true;  // its only schedule
+  if (regional(s)) return !s->seg_mode;  // chain mode's only schedule
   if (s->material || s->wave == 0) return false;
   const WavePlan p = wave_plan(s);
   if (p.C == 0) return false;
@@ -646,7 +675,7 @@ extern "C" rt_status rt_plan_time_block(int ts_method, long long nsteps, int *st
 extern "C" rt_status rt_plan_schedule(rt_solver *s, long long nsteps, int *steps_per_pass, int *level_waves,
                                       int *wgs_per_cu, double *estimated_ms) {
   if (!s || nsteps < 0) return fail(s, RT_ERR_ARG, "rt_plan_schedule: bad argument");
-  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_plan_schedule: a region handle always runs the wavefront");
+  if (regional(s)) return fail(s, RT_ERR_STATE, "rt_plan_schedule: a region handle's schedule is not planned");
   Schedule sc;
   if (s->scheme == SCHEME_BDF2) sc = plan_schedule(run_geom(s), nsteps);
   if (steps_per_pass) *steps_per_pass = sc.T ? sc.T : s->T;
@@ -678,7 +707,7 @@ void rtsn_detail::end_plan(rt_solver *s) {
 }
 
 static bool plan_allowed(const rt_solver *s) {
-  if (s->scheme != SCHEME_BDF2 || s->planned || s->Tpipe || use_wavefront(s)) return false;
+  if (s->scheme != SCHEME_BDF2 || s->planned || s->Tpipe || regional(s) || use_wavefront(s)) return false;
   return !(s->T_set || s->lw_set || s->seg_set || s->pipe_set);  // the caller chose (part of) the schedule
 }
 

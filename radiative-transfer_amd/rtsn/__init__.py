@@ -23,4 +23,5 @@ from .api import (  # noqa: F401
     quadrature,
     regions_load,
     regions_plan,
+    regions_plan_segments,
 )

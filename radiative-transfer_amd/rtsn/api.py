@@ -96,6 +96,7 @@ def lib():
         rp = C.POINTER(rt_region)
         L.rt_regions_plan.argtypes = [rp, C.c_int, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
         L.rt_regions_plan_steps.argtypes = [rp, C.c_int, C.c_int, C.c_int, C.c_longlong] + [C.POINTER(C.c_int)] * 3
+        L.rt_regions_plan_segments.argtypes = [rp, C.c_int, C.c_int] + [C.POINTER(C.c_int)] * 3
         L.rt_regions_load.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(rp), C.POINTER(C.c_int)]
         L.rt_regions_free.argtypes = [rp]
         L.rt_regions_free.restype = None
@@ -142,6 +143,7 @@ def lib():
         L.rt_get_map_form.argtypes = [vp, C.POINTER(C.c_int)]
         L.rt_debug_fail_launch.argtypes = [vp, C.c_int]
         L.rt_debug_set_transfer_chunk.argtypes = [vp, C.c_longlong]
+        L.rt_debug_set_segment_cells.argtypes = [vp, C.c_int]
         L.rt_get_level_waves.argtypes = [vp, C.POINTER(C.c_int)]
         L.rt_set_wavefront.argtypes = [vp, C.c_int]
         L.rt_get_wavefront.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -265,6 +267,23 @@ def regions_plan(regions, reflective: bool = False, max_waves: int = 8, nsteps: 
     _check(lib().rt_regions_plan_steps(arr, len(regions), int(bool(reflective)), int(max_waves), int(nsteps),
                                        C.byref(c), C.byref(w), C.byref(n)), "rt_regions_plan_steps")
     return {"cells_per_lane": c.value, "waves": w.value, "lanes": n.value}
+
+
+def regions_plan_segments(regions, target_cells: int) -> dict:
+    """rt_regions_plan_segments (host only): the segments a region handle in segment mode cuts
+    its lines into at target_cells cells per segment -- {"segments", "first_cell" (segments + 1,
+    physical cells left to right), "segment_region" (segments)}; RtError status 3 unless N and
+    every region's first cell are multiples of 16."""
+    keep: list = []
+    arr = _region_structs([dict(r, group_kappa=None) for r in regions], 0, keep)
+    n = C.c_int()
+    none = C.POINTER(C.c_int)()
+    _check(lib().rt_regions_plan_segments(arr, len(regions), int(target_cells), C.byref(n), none, none),
+           "rt_regions_plan_segments")
+    first, reg = (C.c_int * (n.value + 1))(), (C.c_int * n.value)()
+    _check(lib().rt_regions_plan_segments(arr, len(regions), int(target_cells), C.byref(n), first, reg),
+           "rt_regions_plan_segments")
+    return {"segments": n.value, "first_cell": list(first), "segment_region": list(reg)}
 
 
 def regions_load(filename, table_dir: Optional[str] = None, G: Optional[int] = None):
@@ -760,6 +779,11 @@ class Solver:
     def debug_fail_launch(self, after: int):
         """rt_debug_fail_launch: the pipelined sub-launch after `after` more fails (-1: off)."""
         _check(lib().rt_debug_fail_launch(self._h, int(after)), "rt_debug_fail_launch", self._h)
+
+    def debug_set_segment_cells(self, cells: int):
+        """rt_debug_set_segment_cells: a segment-mode region handle plans its segments for
+        `cells` cells per segment (0: the segmentation's target again)."""
+        _check(lib().rt_debug_set_segment_cells(self._h, int(cells)), "rt_debug_set_segment_cells", self._h)
 
     def debug_set_transfer_chunk(self, doubles: int):
         """rt_debug_set_transfer_chunk: host transfers in pieces of at most `doubles` doubles
