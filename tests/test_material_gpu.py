@@ -121,15 +121,51 @@ def planck_rel(a, b, T, last):
     return float(np.max(np.where(den > 0, num / np.where(den > 0, den, 1.0), num)))
 
 
-def compare(gpu, orc, tol=1e-10):
+def field_floor_of(T, Gl, last):
+    """The floor of compare(..., field_floor=True) per group of a handle: planck_rel's floor of
+    the remainder group (last: the handle holds group G-1), 1e-3 a c T^4 at the hottest cell, and
+    none for every other group.  (planck_rel's 1e-4 a c T^4 for the other groups is NOT carried
+    over to the fields: on the benchmark's grid 39 of them -- the Rayleigh-Jeans groups below
+    ~0.02 keV and the last Wien group -- lie 1e3..8e6 below it, and their fields are well
+    conditioned: they stay measured against their own maximum.)"""
+    floor = np.zeros(Gl)
+    if last:
+        floor[-1] = 1e-3 * max([grey(t) for t in np.asarray(T)] + [0.0])
+    return floor
+
+
+def floored_rel(a, b, group_axis, floor):
+    """per_group_rel with group g's max|b| no smaller than floor[g]."""
+    a = np.moveaxis(np.asarray(a, dtype=np.float64), group_axis, 0)
+    b = np.moveaxis(np.asarray(b, dtype=np.float64), group_axis, 0)
+    G = a.shape[0]
+    num = np.abs(a - b).reshape(G, -1).max(axis=1)
+    den = np.maximum(np.abs(b).reshape(G, -1).max(axis=1), floor)
+    return float(np.max(np.where(den > 0, num / np.where(den > 0, den, 1.0), num)))
+
+
+def compare(gpu, orc, tol=1e-10, field_floor=False):
     """T(x) to 1e-12; the fields, B_g(T), the next emission Beff (B plus the owed share: the
-    device's dB/dT against the oracle's) and the owed energy per group to tol."""
+    device's dB/dT against the oracle's) and the owed energy per group to tol.
+    field_floor: psi and ends of the grey remainder group are measured against no less than
+    planck_rel's floor for that group's emission (field_floor_of), phi against W times it -- a
+    field whose emission is a rounding remainder of a c T^4 (the remainder group on a grid
+    reaching far into the Wien tail) is conditioned no better than that emission."""
+    last = orc.g_lo + orc.Gl == orc.G
+    if field_floor:
+        floor = field_floor_of(orc.temperature(), orc.Gl, last)
+        W = float(np.sum(orc.quad()[1]))
+        fields = {"psi": floored_rel(gpu.psi(), orc.psi(), 1, floor),
+                  "ends": floored_rel(gpu.ends(), orc.ends(), 1, floor),
+                  "phi": floored_rel(gpu.moments()[0], orc.moments()[0], 0, W * floor)}
+    else:
+        fields = {"psi": per_group_rel(gpu.psi(), orc.psi(), 1),
+                  "ends": per_group_rel(gpu.ends(), orc.ends(), 1),
+                  "phi": per_group_rel(gpu.moments()[0], orc.moments()[0], 0)}
     err = {"T": float(np.max(np.abs(gpu.temperature() - orc.temperature()) / np.abs(orc.temperature()))),
-           "psi": per_group_rel(gpu.psi(), orc.psi(), 1),
-           "ends": per_group_rel(gpu.ends(), orc.ends(), 1),
-           "phi": per_group_rel(gpu.moments()[0], orc.moments()[0], 0),
-           "B": planck_rel(gpu.cell_planck(), orc.cell_planck(), orc.temperature(), orc.g_lo + orc.Gl == orc.G),
-           "Beff": planck_rel(gpu.cell_emission(), orc.cell_emission(), orc.temperature(), orc.g_lo + orc.Gl == orc.G)}
+           **fields,
+           "B": planck_rel(gpu.cell_planck(), orc.cell_planck(), orc.temperature(), last),
+           "Beff": planck_rel(gpu.cell_emission(), orc.cell_emission(), orc.temperature(), last)}
     tr_g, tr_o = gpu.material_transit(), orc.material_transit()
     scale = max(float(np.abs(tr_o).max()), 1e-300)
     err["transit"] = float(np.abs(tr_g - tr_o).max() / scale) if np.abs(tr_o).max() > 0 else float(np.abs(tr_g).max())
