@@ -385,6 +385,20 @@ rt_status rt_material_enable(rt_solver *s, double rho_cv, const double *T_cells)
  * The balance read-outs (rt_get_balance*) are not part of the coupling on any handle: their
  * emission term uses the configured T (a region's T), not T(x). */
 rt_status rt_material_enable_regions(rt_solver *s, const double *rho_cv, int nregions, const double *T_cells);
+/* The same coupling on a region handle in SEGMENT mode (long lines; rt_create_regions on a
+ * layout no chain admits, or after rt_set_wavefront(s, 0)): the same arguments, checks and
+ * statuses as rt_material_enable_regions, and everything said there holds but the coupled step,
+ * which is one launch of the line walk: every wave walks its 64 lines whole, cell 0 to N - 1,
+ * across the segment edges of the current plan, reloading the cell map at each segment's first
+ * cell (with the reflective left boundary the same wave then walks the mu > 0 half).  Per
+ * (cell, step) the arithmetic is the chain's: results are bitwise those of a chain-mode handle
+ * where one fits, and do not depend on the segment plan.  RT_ERR_STATE on a handle without
+ * regions (the call there is rt_material_enable) and on a region handle in chain mode (the call
+ * there is rt_material_enable_regions).  While the coupling is on, rt_set_wavefront returns
+ * RT_ERR_STATE (the handle stays in segment mode); rt_set_time_block, rt_set_segmentation and
+ * rt_debug_set_segment_cells are accepted and plan the segments again, which the next step
+ * walks.  No choice between chain and walk is made for the caller: the handle's mode decides. */
+rt_status rt_material_enable_segments(rt_solver *s, const double *rho_cv, int nregions, const double *T_cells);
 /* The emission's stiffness at the current T(x): number = dt W sum_g rho kappa_g
  * dB_g/dT(T_max) / rho_cv over ALL G groups (a shard reports the whole configuration's
  * number); the implicit update scales the explicit change by 1 / (1 + number) at the
@@ -481,17 +495,25 @@ void rt_regions_free(rt_region *r);
  * it (with nothing queued and no material coupling, else RT_ERR_STATE), and
  * rt_set_wavefront(s, 1 or 2) goes back to the chain where one fits (else RT_ERR_STATE) after
  * draining the pipeline.  rt_get_wavefront reports active = 0 in segment mode.
- * RT_ERR_STATE on every region handle: rt_material_enable (material coupling is
- * rt_material_enable_regions, one heat capacity per region), rt_set_level_waves,
+ * Material coupling exists in both modes, one heat capacity per region, and the mode picks the
+ * call: rt_material_enable_regions in chain mode (the coupled step is the wavefront chain),
+ * rt_material_enable_segments in segment mode (the coupled step is the line walk); each
+ * returns RT_ERR_STATE in the other mode and names the other call.  A coupled handle keeps
+ * its mode: rt_set_wavefront (any value) returns RT_ERR_STATE on a coupled segment-mode
+ * handle, rt_set_wavefront(0) on a coupled chain-mode handle; rt_advance and rt_solve return
+ * RT_ERR_STATE as on every coupled handle.
+ * RT_ERR_STATE on every region handle: rt_material_enable, rt_set_level_waves,
  * rt_plan_schedule.
- * RT_ERR_STATE in chain mode: rt_set_time_block, rt_set_pipeline, rt_set_segmentation, and
- * rt_set_wavefront(0) where the layout is not admissible for segments.
+ * RT_ERR_STATE in chain mode: rt_set_time_block, rt_set_pipeline, rt_set_segmentation,
+ * rt_material_enable_segments, and rt_set_wavefront(0) where the layout is not admissible for
+ * segments.
  * RT_ERR_STATE in segment mode: rt_set_pipeline(0) (1 and 2 both mean the pipelined
- * schedule), rt_set_time_block beyond 16, rt_material_enable_regions (the coupled pass is an
- * aligned pass).  rt_set_time_block (1..8, 10, 12, 16; default 16) and rt_set_segmentation
- * work: the workgroups-per-CU target gives the cells per segment a uniform line would get,
- * which is rt_regions_plan_segments' target_cells; rt_sweep_geometry reports the planned
- * segments.  rt_set_map_form never selects the lean maps on a region handle.
+ * schedule), rt_set_time_block beyond 16, rt_material_enable_regions.  rt_set_time_block
+ * (1..8, 10, 12, 16; default 16) and rt_set_segmentation work, coupled or not: the
+ * workgroups-per-CU target gives the cells per segment a uniform line would get, which is
+ * rt_regions_plan_segments' target_cells; rt_sweep_geometry reports the planned segments (a
+ * coupled handle's walk reads the plan's tables; its results do not depend on the plan,
+ * bitwise).  rt_set_map_form never selects the lean maps on a region handle.
  * rt_set_wavefront_cells with a C that is not admissible falls back to the plan's;
  * rt_set_wavefront_waves re-plans (RT_ERR_PARAM, nothing changed, when no chain fits any
  * more).  rt_get_group_data returns region 0's B, dBdT and kappa. */

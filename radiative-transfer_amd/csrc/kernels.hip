@@ -476,6 +476,111 @@ __global__ __launch_bounds__(64) void sweep_block_kernel(SegArgs a) {
   }
 }
 
+// The material-coupled step of a slab of regions on long lines (segment mode): ONE step of
+// every line in one launch.  Within one step the segments of a line depend on each other in
+// order (segment s starts from segment s - 1's exit state of the SAME step), so the pipelined
+// schedule has nothing to overlap: it would be Sg launches of one position each.  Here a wave
+// owns 64 lines and walks them whole, cell 0 to N - 1 in the upwind frame, in chunks of 16 rows
+// (sweep_chunk with the CB scale, T = 1): the carried state stays in registers across segment
+// edges -- no aggregate slot is read or written -- and the rows and their emission scale are
+// prefetched across the edges as inside a segment.  Every segment edge is a multiple of 16
+// (regions::plan_segments), so a chunk lies in one segment, and at a segment's first chunk
+// (workgroup-uniform) the wave reloads the cell map from that segment's region's unit-B set.
+// grid: 2 Q (half, 64-line group), or Q with the reflective left boundary: the same wave then
+// walks the mu < 0 half and, from the exit state it holds, the mu > 0 half -- the head inflow
+// by MODE 2's rule with Xo that state, the head cell on region 0's head map.  No fused angular
+// sums (phi comes from the moments kernels after the step), so no LDS.
+template <int S>
+__global__ __launch_bounds__(64) void sweep_walk_kernel(SegArgs a) {
+  constexpr int K = SchemeDim<S>::K;
+  constexpr int WN = map_count<S>();
+  constexpr int C = chunk_cells(S, 1);
+  static_assert(C == kSweepCells, "a chunk must lie inside one segment (edges are multiples of 16)");
+  const int lane = threadIdx.x;
+  const size_t stride = static_cast<size_t>(a.Lpad);
+  const int q = a.reflective ? static_cast<int>(blockIdx.x) : static_cast<int>(blockIdx.x) % a.Q;
+  const int h0 = a.reflective ? 0 : static_cast<int>(blockIdx.x) / a.Q;
+  const int h1 = a.reflective ? 2 : h0 + 1;
+  const int ell = q * 64 + lane;
+  const int row_bytes = a.Lpad * static_cast<int>(sizeof(double2));
+  const int voff = lane * static_cast<int>(sizeof(double2));
+  const double *bl = a.bcell + min(ell / a.H, a.Gl - 1);  // padding lanes read a clamped, unused value
+  double X[1][K], Z[1][K];
+#pragma unroll
+  for (int r = 0; r < K; ++r) Z[0][r] = 0.0;  // (no pending correction: corr is false)
+  {
+    const double v = a.bdry[static_cast<size_t>(h0) * stride + ell];
+    const double b[4] = {v, v, v, v};
+    head_state<S>(b, X[0]);
+  }
+  const auto phisum = [](const double (&)[C], int, int) {};
+  for (int half = h0; half < h1; ++half) {  // wave-uniform
+    const bool neg = half == 0;
+    const bool refl_head = half == 1 && a.reflective;
+    if (refl_head) {  // solver.cpp:677-684: the mirror line's outflow of this step, held in X
+      double b[4];
+      if constexpr (S == SCHEME_BDF2) {
+        b[0] = X[0][1];
+        b[1] = X[0][2];
+        b[2] = X[0][3];
+        b[3] = X[0][4];
+      } else {
+        b[0] = b[1] = b[2] = b[3] = X[0][K - 1];
+      }
+      head_state<S>(b, X[0]);
+    }
+    const double2 *Eh = a.E + static_cast<size_t>(half) * a.Nrow * stride + q * 64;
+    auto rows = [&](int k0) { return rows_rsrc<C>(Eh + static_cast<size_t>(k0) * stride, row_bytes); };
+    auto bload = [&](int k) -> double {  // B_g(T(x)) of row k: physical cell N - 1 - k for mu < 0
+      const int kk = min(k, a.N - 1);
+      return bl[static_cast<size_t>(neg ? a.N - 1 - kk : kk) * a.Gl];
+    };
+    double ein[C], eout[C], bv[C];
+    {
+      const __amdgpu_buffer_rsrc_t R0 = rows(0);
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const double2 v = row_load(R0, voff, c * row_bytes);
+        ein[c] = v.x;
+        eout[c] = v.y;
+        bv[c] = bload(c);
+      }
+    }
+    double h_oi = 0.0, h_oo = 0.0;
+    if (refl_head) {  // the head cell (physical cell 0) on region 0's head map
+      h_oi = ein[0];
+      h_oo = eout[0];
+      head_cell<S, 1>(a.hmap + ell, stride, X, h_oi, h_oo, bv[0]);
+    }
+    const int *sf = a.seg_first + half * (a.Sg + 1);
+    const int *sr = a.seg_region + half * a.Sg;
+    int s = 0, edge = sf[1];  // the first cell of segment s + 1
+    double W[WN];
+    auto load_map = [&]() {  // the segment's region's rows of [nregions][2][WN][Lpad]
+      const double *mp = a.map + (static_cast<size_t>(sr[s]) * 2 + half) * WN * stride + ell;
+#pragma unroll
+      for (int n = 0; n < WN; ++n) W[n] = mp[n * stride];
+    };
+    load_map();
+    int k0 = 0;
+    for (; k0 + C < a.N; k0 += C) {  // full chunks with a successor
+      if (k0 == edge && s + 1 < a.Sg) {
+        ++s;
+        edge = sf[s + 1];
+        load_map();
+      }
+      sweep_chunk<S, 1, 2, C, false, true>(W, ein, eout, bv, X, false, Z, refl_head && k0 == 0, h_oi, h_oo, rows(k0),
+                                           rows(k0 + C), voff, row_bytes, C, k0, bload, phisum);
+    }
+    if (k0 == edge && s + 1 < a.Sg) {
+      ++s;
+      load_map();
+    }
+    sweep_chunk<S, 1, 2, C, true, true>(W, ein, eout, bv, X, false, Z, refl_head && k0 == 0, h_oi, h_oo, rows(k0),
+                                        rows(k0), voff, row_bytes, a.N - k0, k0, bload, phisum);
+  }
+}
+
 // ------------------------------------------------------------------------
 // Non-hot kernels: state initialisation, layout conversion, moments
 // ------------------------------------------------------------------------
@@ -1839,6 +1944,20 @@ hipError_t launch_sweep(int scheme, int T, int mode, const SegArgs &a, int grid,
     case SCHEME_CN: return launch_s<SCHEME_CN>(T, mode, a, grid, st);
     default: return launch_s<SCHEME_BDF2>(T, mode, a, grid, st);
   }
+}
+
+hipError_t launch_walk(int scheme, const SegArgs &a, int grid, hipStream_t st) {
+  // the kernel indexes by these: checked here
+  if (!a.bcell || !a.seg_first || !a.seg_region || !a.map || !a.hmap || a.Gl < 1 || a.H < 1 || a.Sg < 1 || a.Q < 1)
+    return hipErrorInvalidValue;
+  if (a.N < kSweepCells || a.N % kSweepCells || a.N > a.Nrow || a.Lpad != 64 * a.Q) return hipErrorInvalidValue;
+  if (grid != (a.reflective ? a.Q : 2 * a.Q)) return hipErrorInvalidValue;
+  switch (scheme) {
+    case SCHEME_BE: hipLaunchKernelGGL(sweep_walk_kernel<SCHEME_BE>, dim3(grid), dim3(64), 0, st, a); break;
+    case SCHEME_CN: hipLaunchKernelGGL(sweep_walk_kernel<SCHEME_CN>, dim3(grid), dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL(sweep_walk_kernel<SCHEME_BDF2>, dim3(grid), dim3(64), 0, st, a); break;
+  }
+  return hipGetLastError();
 }
 
 hipError_t launch_fold(int KC, const FoldArgs &f, hipStream_t st) {

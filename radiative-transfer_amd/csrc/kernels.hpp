@@ -97,6 +97,11 @@ enum SweepMode {
   SWEEP_PIPELINED = 2   // one launch of the staggered (pipelined) schedule
 };
 hipError_t launch_sweep(int scheme, int T, int mode, const SegArgs &a, int grid, hipStream_t st);
+// the material-coupled step of a region handle in segment mode (sweep_walk_kernel): one step of
+// every line, each 64-line wave walking its whole lines across the segment edges.  a: seg_args
+// with the unit-B maps (one set per region), bcell, Gl, H, seg_first and seg_region; N and every
+// segment edge multiples of 16; grid = 2 Q, or Q with the reflective left boundary
+hipError_t launch_walk(int scheme, const SegArgs &a, int grid, hipStream_t st);
 // the level-split pipelined BDF2 pass (kernels_split.hip): T levels over `waves` waves
 hipError_t launch_split(int T, int waves, const SegArgs &a, int grid, hipStream_t st);
 hipError_t split_occupancy(int T, int waves, int *workgroups_per_cu);

@@ -302,13 +302,17 @@ extern "C" rt_status rt_set_pipeline(rt_solver *s, int on) {
 extern "C" rt_status rt_set_wavefront(rt_solver *s, int mode) {
   if (!s) return fail(nullptr, RT_ERR_ARG, "rt_set_wavefront: NULL handle");
   if (mode < 0 || mode > 2) return fail(s, RT_ERR_ARG, "rt_set_wavefront: 0 (off), 1 (auto) or 2 (on)");
+  if (regional(s) && s->seg_mode && s->material)
+    return fail(s, RT_ERR_STATE, "rt_set_wavefront: material coupling is on in segment mode (rt_material_enable_segments): "
+                                 "the coupled step stays the line walk");
   if (regional(s) && mode == 0) {  // chain mode -> segment mode, where the layout admits segments
     if (s->seg_mode) return RT_OK;
     if (!regions::segments_admissible(s->first_cell))
       return fail(s, RT_ERR_STATE, "rt_set_wavefront: this region handle runs the wavefront only (segments need N and "
                                    "every region's first cell on multiples of 16)");
     if (s->material)
-      return fail(s, RT_ERR_STATE, "rt_set_wavefront: material coupling is on, and segment mode has no coupled pass");
+      return fail(s, RT_ERR_STATE, "rt_set_wavefront: material coupling is on in chain mode: the coupled step stays the "
+                                   "wavefront chain (rt_material_enable_segments couples a handle already in segment mode)");
     if (s->wqueued || s->queued)
       return fail(s, RT_ERR_STATE, "rt_set_wavefront: steps are queued; read the state out or rt_finish first");
     HIP_TRY(s, hipSetDevice(s->device));

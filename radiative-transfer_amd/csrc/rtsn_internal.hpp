@@ -458,6 +458,7 @@ rt_status complete(rt_solver *s);
 rt_status finalize(rt_solver *s);
 rt_status wave_flush(rt_solver *s);
 rt_status wave_coupled_pass(rt_solver *s);  // a region handle's material-coupled step (one launch)
+rt_status walk_coupled_pass(rt_solver *s);  // ... in segment mode: the line walk (one launch)
 WavePlan wave_plan(const rt_solver *s);
 void end_plan(rt_solver *s);  // the planned schedule gives way to the handle's own
 bool use_wavefront(const rt_solver *s);

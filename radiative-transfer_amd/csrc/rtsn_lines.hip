@@ -432,7 +432,9 @@ rt_status rtsn_detail::ensure_segments(rt_solver *s) {
 // block and the kind of pass it runs.
 
 rt_status rtsn_detail::resegment(rt_solver *h, bool aligned) {
-  if (h->material || h->pending || h->Tpipe) return RT_OK;
+  // (a coupled plain handle keeps the segments rt_material_enable sized; a coupled region
+  // handle in segment mode plans again: its walk reads whatever plan the tables hold)
+  if ((h->material && !h->seg_mode) || h->pending || h->Tpipe) return RT_OK;
   int w = 0;
   if (rt_status st = segment_target(h, &w)) return st;
   const int key = aligned ? -w : w;  // which kind of pass the segments were sized for

@@ -92,24 +92,27 @@ static void material_common(rt_solver *s) {
   for (double w : wt_all) s->wsum_all += w;
 }
 
-// Coupling on a slab of regions: the coupled step is the REG && CB wavefront chain on unit-B
-// maps (one set per region), the material kernels take each cell's own sigma_g(x) and
-// rho_cv(x).  No segment buffers, fused sums or correction tables: phi comes from the moments
-// kernels after each step.
-extern "C" rt_status rt_material_enable_regions(rt_solver *s, const double *rho_cv, int nregions,
-                                                const double *T_cells) {
-  if (!s) return fail(nullptr, RT_ERR_ARG, "rt_material_enable_regions: NULL handle");
-  if (!rho_cv) return fail(s, RT_ERR_ARG, "rt_material_enable_regions: NULL rho_cv");
+// Coupling on a slab of regions: the coupled step is the REG && CB wavefront chain (chain mode)
+// or the line walk (segment mode, sweep_walk_kernel) on unit-B maps (one set per region), the
+// material kernels take each cell's own sigma_g(x) and rho_cv(x).  No fused sums or correction
+// tables: phi comes from the moments kernels after each step.
+
+// the argument checks rt_material_enable_regions and rt_material_enable_segments share (s not NULL)
+static rt_status region_coupling_args(rt_solver *s, const char *fn, const double *rho_cv, int nregions) {
+  if (!rho_cv) return fail(s, RT_ERR_ARG, std::string(fn) + ": NULL rho_cv");
   const int R = regional(s) ? static_cast<int>(s->regions.size()) : 1;
   if (nregions != R)
-    return fail(s, RT_ERR_ARG, "rt_material_enable_regions: nregions must be the handle's " + std::to_string(R));
+    return fail(s, RT_ERR_ARG, std::string(fn) + ": nregions must be the handle's " + std::to_string(R));
   for (int k = 0; k < R; ++k)
     if (!(rho_cv[k] > 0.0) || !std::isfinite(rho_cv[k]))
-      return fail(s, RT_ERR_ARG, "rt_material_enable_regions: every rho_cv must be > 0");
-  if (!regional(s)) return rt_material_enable(s, rho_cv[0], T_cells);
-  if (s->seg_mode)
-    return fail(s, RT_ERR_STATE, "rt_material_enable_regions: the handle is in segment mode, which has no coupled pass "
-                                 "(the coupled step runs on the wavefront chain)");
+      return fail(s, RT_ERR_ARG, std::string(fn) + ": every rho_cv must be > 0");
+  return RT_OK;
+}
+
+// ... and their body, on a region handle in either mode: the buffers, the unit-B maps, T0, the
+// region tables and the first emission
+static rt_status enable_region_coupling(rt_solver *s, const double *rho_cv, const double *T_cells) {
+  const int R = static_cast<int>(s->regions.size());
   if (s->p.use_correction && s->p.V != 0.0)
     return fail(s, RT_ERR_PARAM, "material coupling needs the v/c correction off (V = 0 or use_correction = 0)");
   HIP_TRY(s, hipSetDevice(s->device));
@@ -168,6 +171,31 @@ extern "C" rt_status rt_material_enable_regions(rt_solver *s, const double *rho_
   HIP_TRY(s, hipStreamSynchronize(s->stream));  // T0 dies at return
   s->material = true;  // from here the chain is the one-step plan's (region_wave_plan)
   return RT_OK;
+}
+
+extern "C" rt_status rt_material_enable_regions(rt_solver *s, const double *rho_cv, int nregions,
+                                                const double *T_cells) {
+  if (!s) return fail(nullptr, RT_ERR_ARG, "rt_material_enable_regions: NULL handle");
+  if (rt_status st = region_coupling_args(s, "rt_material_enable_regions", rho_cv, nregions)) return st;
+  if (!regional(s)) return rt_material_enable(s, rho_cv[0], T_cells);
+  if (s->seg_mode)
+    return fail(s, RT_ERR_STATE, "rt_material_enable_regions: the handle is in segment mode, which takes "
+                                 "rt_material_enable_segments (the coupled step is the line walk there, not the "
+                                 "wavefront chain)");
+  return enable_region_coupling(s, rho_cv, T_cells);
+}
+
+extern "C" rt_status rt_material_enable_segments(rt_solver *s, const double *rho_cv, int nregions,
+                                                 const double *T_cells) {
+  if (!s) return fail(nullptr, RT_ERR_ARG, "rt_material_enable_segments: NULL handle");
+  if (rt_status st = region_coupling_args(s, "rt_material_enable_segments", rho_cv, nregions)) return st;
+  if (!regional(s))
+    return fail(s, RT_ERR_STATE, "rt_material_enable_segments: not a region handle; a plain handle takes "
+                                 "rt_material_enable");
+  if (!s->seg_mode)
+    return fail(s, RT_ERR_STATE, "rt_material_enable_segments: the handle is in chain mode, which takes "
+                                 "rt_material_enable_regions");
+  return enable_region_coupling(s, rho_cv, T_cells);
 }
 
 extern "C" rt_status rt_material_enable(rt_solver *s, double rho_cv, const double *T_cells) {
@@ -254,9 +282,9 @@ extern "C" rt_status rt_material_sweep(rt_solver *s, double *d_q) {
   double *q = d_q ? d_q : static_cast<double *>(s->qbuf.p);
   const double *B = static_cast<const double *>(s->Bcell.p), *sig = static_cast<const double *>(s->sigma.p);
   const double *bp = static_cast<const double *>(s->bpart.p);
-  if (regional(s)) {  // one launch of the coupled chain, then phi by the moments kernels
+  if (regional(s)) {  // one launch of the coupled chain (segment mode: the line walk), then phi by the moments kernels
     if ((st = finalize(s))) return st;
-    if ((st = wave_coupled_pass(s))) return st;
+    if ((st = s->seg_mode ? walk_coupled_pass(s) : wave_coupled_pass(s))) return st;
     if ((st = compute_moments(s))) return st;
     HIP_TRY(s, launch_material_q(static_cast<const double *>(s->mom.p), 1, B, static_cast<const double *>(s->rmedium.p),
                                  s->wsum, bp, q, s->Gl, s->p.N, s->stream, static_cast<const int *>(s->cell_region.p)));

@@ -515,6 +515,36 @@ rt_status rtsn_detail::wave_coupled_pass(rt_solver *s) {
   return RT_OK;
 }
 
+// The material-coupled step of a region handle in segment mode: one launch of the line walk
+// (sweep_walk_kernel) over the current segment plan -- the unit-B maps, one set per region,
+// their constants scaled by each cell's emission Beff; the caller has finalized (every position
+// at the same time, nothing queued), and the walk leaves them so.
+rt_status rtsn_detail::walk_coupled_pass(rt_solver *s) {
+  if (!s->seg_mode || !s->seg_tab.p || static_cast<int>(s->seg_region.size()) != s->Sg)
+    return fail(s, RT_ERR_STATE, "regions: no segment plan for the coupled walk");
+  for (int f : s->seg_first)  // a chunk of 16 rows must lie in one segment
+    if (f % kSweepCells) return fail(s, RT_ERR_STATE, "regions: a segment edge is not a multiple of 16");
+  SegArgs a = seg_args(s);
+  a.Gl = s->Gl;
+  a.H = s->H;
+  a.map = static_cast<const double *>(s->map_unit.p);
+  a.hmap = static_cast<const double *>(s->hmap_unit.p);
+  a.bcell = static_cast<const double *>(s->Beff.p);  // the step's linearised emission
+  hipEvent_t e1;
+  rt_status st = event_begin(s, &e1);
+  if (st) return st;
+  const hipError_t e = launch_walk(s->scheme, a, (a.reflective ? 1 : 2) * s->Q, s->stream);
+  if (e != hipSuccess) {
+    event_abort(s, e1);
+    return fail(s, RT_ERR_DEVICE, std::string("coupled walk launch: ") + hipGetErrorString(e));
+  }
+  if ((st = event_end(s, e1))) return st;
+  ++s->state_version;
+  for (long long &t : s->tau) ++t;
+  ++s->target;
+  return RT_OK;
+}
+
 static rt_status wave_advance(rt_solver *s, int nsteps) {
   if (!s->wqueued)
     if (rt_status st = finalize(s)) return st;  // the stored state exact at the requested time

@@ -152,6 +152,7 @@ def lib():
         L.rt_set_wavefront_cells.argtypes = [vp, C.c_int]
         L.rt_material_enable.argtypes = [vp, C.c_double, dp]
         L.rt_material_enable_regions.argtypes = [vp, dp, C.c_int, dp]
+        L.rt_material_enable_segments.argtypes = [vp, dp, C.c_int, dp]
         L.rt_material_sweep.argtypes = [vp, vp]
         L.rt_material_update.argtypes = [vp, vp]
         L.rt_material_step.argtypes = [vp, C.c_int]
@@ -606,6 +607,18 @@ class Solver:
             raise ValueError("material_enable_regions: T_cells must hold N values")
         _check(lib().rt_material_enable_regions(self._h, _dp(rc), int(rc.size), None if T is None else _dp(T)),
                "rt_material_enable_regions", self._h)
+        return self.material_stability()
+
+    def material_enable_segments(self, rho_cv, T_cells=None):
+        """T(x) coupling on a region handle in segment mode (rt_material_enable_segments): the
+        arguments of material_enable_regions; the coupled step is then the one-launch line walk.
+        Returns the stability number (the stiffest region's)."""
+        rc = np.ascontiguousarray(rho_cv, dtype=np.float64).ravel()
+        T = None if T_cells is None else np.ascontiguousarray(T_cells, dtype=np.float64)
+        if T is not None and T.size != self.N:
+            raise ValueError("material_enable_segments: T_cells must hold N values")
+        _check(lib().rt_material_enable_segments(self._h, _dp(rc), int(rc.size), None if T is None else _dp(T)),
+               "rt_material_enable_segments", self._h)
         return self.material_stability()
 
     def material_stability(self) -> float:
