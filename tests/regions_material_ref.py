@@ -20,6 +20,14 @@ With identical regions this is the uniform coupling, which tests/test_regions_ma
 pins to the C oracle's orc_material_*.  The accessors carry the names
 test_material_gpu.compare reads (temperature, psi, ends, moments, cell_planck,
 cell_emission, material_transit, g_lo, Gl, G).
+
+dtype (default np.float64: the above, unchanged): another format, np.longdouble for the material
+regime sweep's truth (tests/material_regime_cases.py), runs the whole step in it -- T, owed, dB,
+Beff, q, b, the update and the root, the sweep as RegionReference's in that dtype -- on the fp64
+inputs cast exactly, with the Planck terms from oracle/planck_np.py in that dtype (the fp64 path
+keeps the C oracle's calls: planck_np in fp64 agrees with them to 2 ulps of the operands, not
+bitwise) and the root bisected, all solving cells at once, until the bracket is at most 4 ulp of
+the dtype.  Every update records which cells solved the root, each cell's dT / T and the T it leaves (history).
 """
 from __future__ import annotations
 
@@ -49,10 +57,12 @@ class _CellSets:
 
 
 class RegionMaterialReference(RegionReference):
-    def __init__(self, oracle_mod, p, regions, rho_cv, T_cells=None, g_lo=0, g_hi=0):
+    def __init__(self, oracle_mod, p, regions, rho_cv, T_cells=None, g_lo=0, g_hi=0, dtype=np.float64):
         import fused_np
         assert not (p["use_correction"] and p["V"] != 0.0)
         self.om, self.p = oracle_mod, p
+        f = self.dtype = np.dtype(dtype).type
+        self.native = f is np.float64  # the C oracle's Planck terms and the scalar root, as before
         M, N = p["M"], p["N"]
         self.M, self.N, self.G = M, N, p["G"]
         self.g_lo, g_hi = g_lo, (g_hi or p["G"])
@@ -64,7 +74,7 @@ class RegionMaterialReference(RegionReference):
         assert self.cell_region.size == N and len(rho_cv) == len(regions)
         self.dx = np.array([r["width"] / r["cells"] for r in regions])
         self.dx_cells = self.dx[self.cell_region]
-        self.rho_cv_cells = np.asarray(rho_cv, dtype=np.float64)[self.cell_region]
+        self.rho_cv_cells = np.asarray(rho_cv, dtype=np.float64)[self.cell_region].astype(f)
         tables = []
         for r in regions:
             pr = dict(p, rho=r["rho"], kappa_grey=r["kappa_grey"], T=r["T"], group_kappa=r["group_kappa"],
@@ -76,9 +86,10 @@ class RegionMaterialReference(RegionReference):
             self.e_edge = g["e_edge"].copy()
             tables.append(dict(B=g["B"][sl], sigma=r["rho"] * g["kappa"][sl], sigma_all=r["rho"] * g["kappa"]))
         self.tables = tables
-        self.sigma_cells = np.stack([tables[r]["sigma"] for r in self.cell_region])          # (N, Gl)
-        self.sigma_all_cells = np.stack([tables[r]["sigma_all"] for r in self.cell_region])  # (N, G)
-        self.W = float(self.wt.sum())
+        self.sigma_cells = np.stack([tables[r]["sigma"] for r in self.cell_region]).astype(f)          # (N, Gl)
+        self.sigma_all_cells = np.stack([tables[r]["sigma_all"] for r in self.cell_region]).astype(f)  # (N, G)
+        self.psi_source = np.asarray(self.psi_source, dtype=f)
+        self.W = f(float(self.wt.sum()))
         self.idx, self.unit_lines, self.lines, self.E = {}, {}, {}, {}
         zeros = np.zeros(h * self.Gl)
         for half in (0, 1):
@@ -86,30 +97,53 @@ class RegionMaterialReference(RegionReference):
             Gi = np.repeat(np.arange(self.Gl), h)
             self.idx[half] = (I, Gi)
             self.unit_lines[half] = [fused_np.LineSet(self.mu[I], t["sigma"][Gi], np.ones(h * self.Gl), zeros, zeros,
-                                                      zeros, 0.0, dx, p["dt"], p["ts_method"], False)
+                                                      zeros, 0.0, dx, p["dt"], p["ts_method"], False, dtype=f)
                                      for t, dx in zip(tables, self.dx)]
             self.lines[half] = _CellSets(self, half)
             reg = self.cell_region[::-1] if half == 0 else self.cell_region
             B_cells = np.stack([tables[r]["B"][Gi] for r in reg], axis=1)  # (lines, N): psi = its region's B_g
-            self.E[half] = np.repeat(B_cells[:, :, None], 2, axis=2).astype(np.float64)
+            self.E[half] = np.repeat(B_cells[:, :, None], 2, axis=2).astype(f)
         self.nsub = 4 if p["ts_method"] == 3 else 1
         # the material state
         self.T = (np.array([regions[r]["T"] for r in self.cell_region], dtype=np.float64) if T_cells is None
-                  else np.array(T_cells, dtype=np.float64))
-        self.dTlast = np.zeros(N)
-        self.owed = np.zeros((N, self.Gl))
-        self.dB = np.zeros((N, self.Gl))
-        self.Bcell = np.zeros((N, self.Gl))
-        self.Beff = np.zeros((N, self.Gl))
-        self.bpart = np.zeros(N)
+                  else np.array(T_cells, dtype=np.float64)).astype(f)
+        self.dTlast = np.zeros(N, dtype=f)
+        self.owed = np.zeros((N, self.Gl), dtype=f)
+        self.dB = np.zeros((N, self.Gl), dtype=f)
+        self.Bcell = np.zeros((N, self.Gl), dtype=f)
+        self.Beff = np.zeros((N, self.Gl), dtype=f)
+        self.bpart = np.zeros(N, dtype=f)
         self.newton_cells = 0  # cells that solved the full emission, over all updates
+        # per update: dict(solved=(N) bool, ratio=(N) dT / T of the linear update, T=(N) after the update)
+        self.history = []
         self._planck()
 
     def _upwind_regions(self, half):
         return np.arange(self.N)  # _sweep's sets[reg[k]]: _CellSets is indexed by the upwind cell
 
     # ---- Planck terms and the owed emission at the current T ----
+    def _planck_terms(self, T, g_lo, g_hi, deriv=False):
+        """(cells, g_hi - g_lo) of kcon B_g (deriv: dB_g/dT) at the temperatures T, in self.dtype."""
+        if self.native:
+            fn = self.om.planck_cell_dBdT if deriv else self.om.planck_cell
+            return np.array([[fn(t, self.e_edge, g) for g in range(g_lo, g_hi)] for t in np.atleast_1d(T)])
+        import planck_np
+        # the cells' T in fp64 decide the branches; T held in a wider dtype enters the arithmetic
+        return planck_np.planck_cells(np.atleast_1d(T), self.e_edge, g_lo, g_hi, self.dtype, deriv)
+
     def _planck(self):
+        if not self.native:
+            f = self.dtype
+            owed = self.owed + self.dB * self.dTlast[:, None]
+            B = self._planck_terms(self.T, self.g_lo, self.g_lo + self.Gl)
+            dB = self._planck_terms(self.T, self.g_lo, self.g_lo + self.Gl, deriv=True)
+            pay = np.where(owed > -B, owed, -B)
+            self.Bcell, self.Beff, self.owed, self.dB = B, B + pay, owed - pay, dB
+            b = np.zeros(self.N, dtype=f)
+            for gl in range(self.Gl):
+                b = b + self.sigma_cells[:, gl] * dB[:, gl]
+            self.bpart = b
+            return
         for c in range(self.N):
             b = 0.0
             for gl in range(self.Gl):
@@ -148,6 +182,33 @@ class RegionMaterialReference(RegionReference):
                 lo = mid
         return 0.5 * (lo + hi)
 
+    def _solve_cells(self, cells, q):
+        """_solve_cell for the cells (indices) at once, in self.dtype: bisection until every
+        bracket is at most 4 ulp of the dtype."""
+        f = self.dtype
+        T, dt, W, rc = self.T[cells], f(self.p["dt"]), self.W, self.rho_cv_cells[cells]
+        sig = self.sigma_all_cells[cells]
+
+        def emission(t):
+            return (sig * self._planck_terms(t, 0, self.G)).sum(axis=1)
+
+        A = q + W * emission(T)
+        hi0 = T + dt * A / rc
+        out = hi0.copy()
+        live = hi0 > 0
+        lo, hi = np.zeros_like(hi0), np.where(live, hi0, f(1))
+        tol = 4 * np.finfo(f).eps
+        for _ in range(40000):
+            mid = f(0.5) * (lo + hi)
+            live = live & (hi - lo > tol * hi) & (lo < mid) & (mid < hi)
+            if not live.any():
+                break
+            fm = rc * (mid - T) + dt * W * emission(np.where(live, mid, f(1))) - dt * A
+            up = live & (fm > 0)
+            hi = np.where(up, mid, hi)
+            lo = np.where(live & ~up, mid, lo)
+        return np.where(hi0 > 0, f(0.5) * (lo + hi), out)
+
     # ---- the coupled step ----
     def material_sweep(self):
         """One coupled full step with the emission Beff; returns this solver's [q, b] (2N)."""
@@ -158,9 +219,32 @@ class RegionMaterialReference(RegionReference):
 
     def material_update(self, qb):
         N, dt, W = self.N, self.p["dt"], self.W
+        if not self.native:
+            f = self.dtype
+            qb = np.asarray(qb, dtype=f)
+            q, b, T = qb[:N], qb[N:], self.T
+            dT = f(dt) * q / (self.rho_cv_cells + f(dt) * W * b)
+            solve = ~(dT <= f(NEWTON_FRAC) * T)
+            with np.errstate(all="ignore"):
+                self.history.append(dict(solved=solve.copy(), ratio=np.asarray(dT / T, dtype=np.float64)))
+            Tn, dTl = T + dT, dT.copy()
+            cells = np.flatnonzero(solve)
+            if cells.size:
+                Tr = self._solve_cells(cells, q[cells])
+                self.owed[cells] += self._planck_terms(Tr, self.g_lo, self.g_lo + self.Gl) - self.Bcell[cells]
+                Tn[cells], dTl[cells] = Tr, 0
+                self.newton_cells += int(cells.size)
+            self.T, self.dTlast = Tn, dTl
+            self.history[-1]["T"] = np.asarray(Tn, dtype=np.float64)
+            self._planck()
+            return
+        solved, ratio = np.zeros(N, dtype=bool), np.zeros(N)
+        self.history.append(dict(solved=solved, ratio=ratio))
         for c in range(N):
             q, b, T = qb[c], qb[N + c], self.T[c]
             dT = dt * q / (self.rho_cv_cells[c] + dt * W * b)
+            ratio[c] = dT / T if T != 0 else np.copysign(np.inf, dT)
+            solved[c] = not dT <= NEWTON_FRAC * T
             if dT <= NEWTON_FRAC * T:
                 self.T[c] = T + dT
                 self.dTlast[c] = dT
@@ -171,6 +255,7 @@ class RegionMaterialReference(RegionReference):
                 self.T[c] = Tn
                 self.dTlast[c] = 0.0
                 self.newton_cells += 1
+        self.history[-1]["T"] = self.T.copy()
         self._planck()
 
     def material_step(self, n=1):
@@ -179,7 +264,7 @@ class RegionMaterialReference(RegionReference):
 
     # ---- read-outs (test_material_gpu.compare's names) ----
     def ends(self):
-        out = np.empty((self.M, self.Gl, self.N, 2))
+        out = np.empty((self.M, self.Gl, self.N, 2), dtype=self.dtype)
         for half in (0, 1):
             I, Gi = self.idx[half]
             E = self.E[half]
@@ -193,12 +278,14 @@ class RegionMaterialReference(RegionReference):
 
     def psi(self):
         e = self.ends()
-        return 0.5 * (e[..., 0] + e[..., 1])
+        return self.dtype(0.5) * (e[..., 0] + e[..., 1])
 
     def moments(self):
         psi = self.psi()
-        return (np.einsum("i,igc->gc", self.wt, psi), np.einsum("i,igc->gc", self.mu * self.wt, psi),
-                np.einsum("i,igc->gc", self.wt[self.mu > 0], psi[self.mu > 0]))
+        wt = np.asarray(self.wt, dtype=self.dtype)
+        mw = np.asarray(self.mu, dtype=self.dtype) * wt
+        return (np.einsum("i,igc->gc", wt, psi), np.einsum("i,igc->gc", mw, psi),
+                np.einsum("i,igc->gc", wt[self.mu > 0], psi[self.mu > 0]))
 
     def quad(self):
         return self.mu, self.wt
@@ -213,7 +300,7 @@ class RegionMaterialReference(RegionReference):
         return self.Beff.T.copy()
 
     def material_transit(self):
-        return self.p["dt"] * self.W * (self.sigma_cells * ((self.Beff - self.Bcell) + self.owed)).sum(axis=1)
+        return self.dtype(self.p["dt"]) * self.W * (self.sigma_cells * ((self.Beff - self.Bcell) + self.owed)).sum(axis=1)
 
 
 def region_energy(s, dx_cells, rho_cv_cells, c_light):
