@@ -399,6 +399,36 @@ rt_status rt_material_enable_regions(rt_solver *s, const double *rho_cv, int nre
  * rt_debug_set_segment_cells are accepted and plan the segments again, which the next step
  * walks.  No choice between chain and walk is made for the caller: the handle's mode decides. */
 rt_status rt_material_enable_segments(rt_solver *s, const double *rho_cv, int nregions, const double *T_cells);
+/* A temperature-dependent opacity on a coupled region handle in segment mode (after
+ * rt_material_enable_segments; a uniform slab is a one-region handle taken to segment mode with
+ * rt_set_wavefront(s, 0)).  Region k's cells take sigma_g(x) = rho_k kappa_{k,g} f(x) with
+ *   f(x) = clamp((T(x) / T_ref[k])^(-exponent[k]), scale_min, scale_max),
+ * one f per cell for all groups (a group shard needs nothing from the others: every rank holds
+ * the same T(x)).  Where T <= 0 or T is not finite the ratio counts as 0+: scale_max for an
+ * exponent > 0, scale_min for one < 0, clamp(1) for 0.  exponent == NULL with nregions == 0
+ * turns the law off.
+ * The opacity is LAGGED: f is formed from T^n when the law is set and after every update, and
+ * everything in step n uses sigma(T^n) -- the sweep, q, b, the S(T') of the Newton path (f held
+ * fixed during the solve), rt_get_material_transit, rt_material_stability (f at each region's
+ * hottest cell) and rt_group_absorption_device.  The owed emission is kept in B units, its
+ * energy dt W sigma_g owed_g: when f changes, the finalised owed emission (owed + dB/dT dT) is
+ * multiplied by f_old / f_new before the payment p_g = max(owed_g, -B_g) is taken -- after an
+ * update, and when the law is set, changed or cleared in mid-run (there on the emission in
+ * transit, p_g + owed_g, paid again by the same rule).  With it the BE energy statement above
+ * holds unchanged.
+ * The coupled step is then one launch of the law form of the line walk: no cell map; every lane
+ * forms its cell's line constants in fp64 from sigma(x) and runs the reference's cell algebra.
+ * With exponent 0 the results equal the map walk's to rounding, not bitwise (the maps are
+ * derived in long double).  Set and cleared before any step, the handle is bitwise as before.
+ * RT_ERR_STATE on a handle without regions and on a region handle in chain mode (the calls to
+ * make instead: rt_create_regions, rt_set_wavefront(s, 0), rt_material_enable_segments), and on
+ * an uncoupled handle in segment mode (rt_material_enable_segments first).  RT_ERR_ARG: nregions
+ * not the handle's, a T_ref that is not finite or not > 0, a non-finite exponent, bounds that
+ * do not satisfy 0 < scale_min <= scale_max < infinity. */
+rt_status rt_material_set_opacity_law(rt_solver *s, const double *exponent, const double *T_ref, int nregions,
+                                      double scale_min, double scale_max);
+/* f(x) of every cell (N, host) as the next step will use it; 1 with the law off. */
+rt_status rt_get_opacity_scale(rt_solver *s, double *f);
 /* The emission's stiffness at the current T(x): number = dt W sum_g rho kappa_g
  * dB_g/dT(T_max) / rho_cv over ALL G groups (a shard reports the whole configuration's
  * number); the implicit update scales the explicit change by 1 / (1 + number) at the

@@ -57,6 +57,49 @@ struct LineConstT {
 };
 using LineConst = LineConstT<double>;
 
+// The constants of one line's cell systems from (c, tau, dt, |mu|, sigma = rho kappa_g, dx): tau
+// the substep (dt / 2 for BDF2, whose const_B takes the full dt), and LC_SC the source of
+// B_g = 1 with no v/c correction, S = 1/2 c tau dx sigma (the caller scales it by B_g and adds
+// the correction's terms; LC_SL is left 0).  One definition for the host's per-region maps
+// (rtsn_lines.hip line_constants, R = long double) and for the walk that forms them per cell
+// from sigma(x) = sigma0 f(x) (kernels.hip sweep_walk_law_kernel, R = double).
+template <class R>
+__host__ __device__ __forceinline__ LineConstT<R> line_constants_unit(R c, R tau, R dt, R m, R sigma, R dx) {
+  LineConstT<R> L{};
+  const R half = R(0.5) * c * tau * dx;
+  L.c[LC_SC] = half * sigma;
+  L.c[LC_SL] = R(0.0);
+  auto inverse = [](R d, R o, R &i0, R &i1) {
+    const R det = d * d + o * o;
+    i0 = d / det;
+    i1 = o / det;
+  };
+  {  // BE(tau)
+    const R a = R(1.0) + c * tau * sigma, b = c * tau * m;
+    L.c[LC_BE_B] = b;
+    inverse((a * dx + b) / R(2.0), b / R(2.0), L.c[LC_BE_I0], L.c[LC_BE_I1]);
+  }
+  {  // CN(tau)
+    const R t = R(0.5) * c * tau * sigma, A = R(0.5) * c * m * tau;
+    const R Bp = R(1.0) + t, Cp = R(1.0) - t;
+    L.c[LC_CN_A] = A;
+    L.c[LC_CN_K1] = R(0.5) * (Cp * dx - A);
+    L.c[LC_CN_K2] = R(0.5) * A;
+    inverse(R(0.5) * (A + Bp * dx), A / R(2.0), L.c[LC_CN_I0], L.c[LC_CN_I1]);
+  }
+  {  // BDF(tau) with const_B from the full dt
+    const R t = c * sigma * tau / R(6.0), Ab = R(1.0) + t, Bc = c * m * dt / R(6.0);
+    const R Cb = R(1.0) - R(4.0) * t, D = t;
+    L.c[LC_BD_BC] = Bc;
+    L.c[LC_BD_Q1] = R(0.5) * (Cb * dx - R(4.0) * Bc);
+    L.c[LC_BD_Q2] = R(2.0) * Bc;
+    L.c[LC_BD_Q3] = R(0.5) * (Bc + D * dx);
+    L.c[LC_BD_Q4] = R(0.5) * Bc;
+    inverse(R(0.5) * (Ab * dx + Bc), R(0.5) * Bc, L.c[LC_BD_I0], L.c[LC_BD_I1]);
+  }
+  return L;
+}
+
 template <class R>
 __host__ __device__ __forceinline__ R src(const LineConstT<R> &L, R ein, R eout) {
   return L.c[LC_SC] + L.c[LC_SL] * (ein + eout);

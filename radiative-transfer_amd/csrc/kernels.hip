@@ -581,6 +581,131 @@ __global__ __launch_bounds__(64) void sweep_walk_kernel(SegArgs a) {
   }
 }
 
+// The line walk with a temperature-dependent opacity (rt_material_set_opacity_law): the cell map
+// then varies from cell to cell and from step to step, so there is no map to hold in registers.
+// Each lane forms its cell's line constants in fp64 from sigma = sigma0[region][group] f(x)
+// (cell.hpp line_constants_unit, the definition the host's long-double maps come from), scales
+// the unit source by the cell's Beff and runs the reference algebra cell_step<S> -- for the
+// reflective head cell cell_step_maybe_head<S> with the mirror's last-substep outflow, what the
+// head map was probed from.  Probing a map per cell would cost K + 3 cell steps to save one.
+// Everything else is sweep_walk_kernel's: the grid and the reflective second half, chunks of C
+// rows with the rows, the emission scale and f(x) (wave-uniform per row) prefetched across
+// segment edges, the carried state in registers; sigma0 and dx are reloaded at a segment's first
+// chunk, where that kernel reloads the map.
+// One chunk: LAST -- no prefetch.  head: the chunk's first cell is the reflective head cell.
+template <int S, int C, bool LAST, typename BL, typename FL>
+__device__ __forceinline__ void walk_law_chunk(const WalkLaw &w, double m, double sig0, double dx, bool neg,
+                                               double (&ein)[C], double (&eout)[C], double (&bv)[C], double (&fv)[C],
+                                               double (&X)[SchemeDim<S>::K], bool head, __amdgpu_buffer_rsrc_t Rw,
+                                               __amdgpu_buffer_rsrc_t Rn, int voff, int row_bytes, int k0,
+                                               const BL &bload, const FL &fload) {
+  constexpr int K = SchemeDim<S>::K;
+  const double hd = 0.5 * dx;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    LineConst L = line_constants_unit<double>(w.c, w.tau, w.dt, m, sig0 * fv[c], dx);
+    L.c[LC_SC] *= bv[c];  // the unit source times the cell's emission
+    double oi, oo;
+    if (S == SCHEME_BDF2 && c == 0 && head)  // wave-uniform
+      cell_step_maybe_head<S>(L, hd, neg, ein[c], eout[c], X, true, X[K - 1], oi, oo);
+    else
+      cell_step<S>(L, hd, neg, ein[c], eout[c], X, oi, oo);
+    row_store(Rw, voff, c * row_bytes, oi, oo);
+    if constexpr (!LAST) {
+      const double2 v = row_load(Rn, voff, c * row_bytes);
+      ein[c] = v.x;
+      eout[c] = v.y;
+      bv[c] = bload(k0 + C + c);
+      fv[c] = fload(k0 + C + c);
+    }
+  }
+}
+
+template <int S>
+__global__ __launch_bounds__(64) void sweep_walk_law_kernel(SegArgs a, WalkLaw w) {
+  constexpr int K = SchemeDim<S>::K;
+  constexpr int C = kSweepCells;
+  const int lane = threadIdx.x;
+  const size_t stride = static_cast<size_t>(a.Lpad);
+  const int q = a.reflective ? static_cast<int>(blockIdx.x) : static_cast<int>(blockIdx.x) % a.Q;
+  const int h0 = a.reflective ? 0 : static_cast<int>(blockIdx.x) / a.Q;
+  const int h1 = a.reflective ? 2 : h0 + 1;
+  const int ell = q * 64 + lane;
+  const int row_bytes = a.Lpad * static_cast<int>(sizeof(double2));
+  const int voff = lane * static_cast<int>(sizeof(double2));
+  const int gl = min(ell / a.H, a.Gl - 1), ip = ell % a.H;  // padding lanes: a clamped, unused group
+  const double *bl = a.bcell + gl;
+  double X[K];
+  {
+    const double v = a.bdry[static_cast<size_t>(h0) * stride + ell];
+    const double b[4] = {v, v, v, v};
+    head_state<S>(b, X);
+  }
+  for (int half = h0; half < h1; ++half) {  // wave-uniform
+    const bool neg = half == 0;
+    const bool refl_head = half == 1 && a.reflective;
+    if (refl_head) {  // solver.cpp:677-684: the mirror line's outflow of this step, held in X
+      double b[4];
+      if constexpr (S == SCHEME_BDF2) {
+        b[0] = X[1];
+        b[1] = X[2];
+        b[2] = X[3];
+        b[3] = X[4];
+      } else {
+        b[0] = b[1] = b[2] = b[3] = X[K - 1];
+      }
+      head_state<S>(b, X);
+    }
+    const double m = fabs(w.mu[neg ? a.H - 1 - ip : a.H + ip]);
+    const double2 *Eh = a.E + static_cast<size_t>(half) * a.Nrow * stride + q * 64;
+    auto rows = [&](int k0) { return rows_rsrc<C>(Eh + static_cast<size_t>(k0) * stride, row_bytes); };
+    auto cell_of = [&](int k) {  // row k: physical cell N - 1 - k for mu < 0 (rows past N - 1 clamped, unused)
+      const int kk = min(k, a.N - 1);
+      return static_cast<size_t>(neg ? a.N - 1 - kk : kk);
+    };
+    auto bload = [&](int k) -> double { return bl[cell_of(k) * a.Gl]; };
+    auto fload = [&](int k) -> double { return w.fscale[cell_of(k)]; };
+    double ein[C], eout[C], bv[C], fv[C];
+    {
+      const __amdgpu_buffer_rsrc_t R0 = rows(0);
+#pragma unroll
+      for (int c = 0; c < C; ++c) {
+        const double2 v = row_load(R0, voff, c * row_bytes);
+        ein[c] = v.x;
+        eout[c] = v.y;
+        bv[c] = bload(c);
+        fv[c] = fload(c);
+      }
+    }
+    const int *sf = a.seg_first + half * (a.Sg + 1);
+    const int *sr = a.seg_region + half * a.Sg;
+    int s = 0, edge = sf[1];  // the first cell of segment s + 1
+    double sig0, dx;
+    auto load_medium = [&]() {  // the segment's region: its opacity of the lane's group, its cell width
+      sig0 = w.rsigma[static_cast<size_t>(sr[s]) * a.Gl + gl];
+      dx = w.rdx[sr[s]];
+    };
+    load_medium();
+    int k0 = 0;
+    for (; k0 + C < a.N; k0 += C) {  // full chunks with a successor
+      if (k0 == edge && s + 1 < a.Sg) {
+        ++s;
+        edge = sf[s + 1];
+        load_medium();
+      }
+      walk_law_chunk<S, C, false>(w, m, sig0, dx, neg, ein, eout, bv, fv, X, refl_head && k0 == 0, rows(k0),
+                                  rows(k0 + C), voff, row_bytes, k0, bload, fload);
+    }
+    if (k0 == edge && s + 1 < a.Sg) {
+      ++s;
+      load_medium();
+    }
+    // (N is a multiple of C: the last chunk is whole)
+    walk_law_chunk<S, C, true>(w, m, sig0, dx, neg, ein, eout, bv, fv, X, refl_head && k0 == 0, rows(k0), rows(k0),
+                               voff, row_bytes, k0, bload, fload);
+  }
+}
+
 // ------------------------------------------------------------------------
 // Non-hot kernels: state initialisation, layout conversion, moments
 // ------------------------------------------------------------------------
@@ -1010,12 +1135,14 @@ __global__ void balance_partials_regions_kernel(const double *phi, const double 
   part[(static_cast<size_t>(rp) * Gl + g) * 2 + 1] = e;
 }
 
+template <bool LAW = false>  // LAW: times the opacity law's fscale[c]
 __global__ void group_absorption_regions_kernel(const double *phi, const double *sigma, const int *cell_region,
-                                                double *out, int Gl, int N) {
+                                                double *out, int Gl, int N, const double *fscale) {
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < N; c += gridDim.x * blockDim.x) {
     const double *sg = sigma + static_cast<size_t>(cell_region[c]) * Gl;
     double s = 0.0;
     for (int g = 0; g < Gl; ++g) s += sg[g] * phi[static_cast<size_t>(c) * Gl + g];
+    if constexpr (LAW) s *= fscale[c];
     out[c] = s;
   }
 }
@@ -1167,9 +1294,33 @@ constexpr double kPlanckPre = 2.0 / ((4.141895e-10 * 4.141895e-10 * 4.141895e-10
 //
 // REG (a slab of regions, PlanckCells.cell_region set): bpart uses the cell's own opacities,
 // sigma_gl(x) = rsigma[cell_region[x]][gl]; nothing else of the kernel depends on the medium.
+//
+// LAW (REG only; the opacity law, PlanckCells.fscale set): sigma_gl(x) = rsigma f(x), f from the
+// cell's T (opacity_scale).  The owed emission is kept in B units and its energy is
+// dt W sigma_g owed_g, so when f changes the finalised owed emission is multiplied by
+// f_old / f_new before the payment is taken.  opacity_scale_kernel, launched ahead of the pass,
+// forms both (fratio = f_old / f_new, f_old fscale as the last pass left it; fscale takes f_new):
+// pow() inside this kernel cost it scratch at its four waves per SIMD.  bpart stays the unscaled
+// sum: material_q_kernel applies f(x) to b with q.
+__device__ __forceinline__ double opacity_scale(double T, double Tref, double n, double lo, double hi) {
+  // T <= 0 or not finite: the ratio counts as 0+
+  const double v = T > 0.0 && isfinite(T) ? pow(T / Tref, -n) : (n > 0.0 ? hi : (n < 0.0 ? lo : 1.0));
+  return fmin(fmax(v, lo), hi);
+}
+
+__global__ void opacity_scale_kernel(PlanckCells pc, const double *T) {
+  for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < pc.N; x += gridDim.x * blockDim.x) {
+    const int rg = pc.cell_region[x];
+    const double f_new = opacity_scale(T[x], pc.law_Tref[rg], pc.law_n[rg], pc.law_min, pc.law_max);
+    pc.fratio[x] = pc.fscale[x] / f_new;
+    pc.fscale[x] = f_new;
+  }
+}
+
 constexpr int kPlanckCells = 64, kPlanckGroups = 32, kPlanckThreads = 256;
-template <bool REG>
+template <bool REG, bool LAW = false>
 __global__ __launch_bounds__(kPlanckThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void planck_cells_kernel(PlanckCells pc, const double *Tc, double *B) {
+  static_assert(REG || !LAW, "the opacity law is a region handle's");
   __shared__ double tile[2][kPlanckCells * (kPlanckGroups + 1)];
   __shared__ double bsum[kPlanckThreads / 64][kPlanckCells];
   __shared__ double rk[65];
@@ -1200,7 +1351,8 @@ __global__ __launch_bounds__(kPlanckThreads) __attribute__((amdgpu_waves_per_eu(
         if (lane < nx) {
 #pragma clang fp contract(off)
           const size_t o = static_cast<size_t>(g0 + j) * pc.N + x0 + lane;
-          const double owed = pc.owed[o] + pc.dB[o] * dT;
+          double owed = pc.owed[o] + pc.dB[o] * dT;
+          if constexpr (LAW) owed = owed * pc.fratio[x0 + lane];
           pay = owed > -b ? owed : -b;
           pc.owed[o] = owed - pay;
           pc.dB[o] = db;
@@ -1728,9 +1880,11 @@ __global__ __launch_bounds__(64 * kRowsWaves) void phi_correction_rows_kernel(Se
 // [part][x][g] (the fused halves and their corrections, or one full phi):
 // one wave per cell, lanes over groups, then a butterfly over the wave.  REG: sigma is
 // [nregions][Gl] and cell x reads the row of its region, sigma_g(x)
-template <bool REG>
+// LAW: sigma_g(x) = sigma[region][g] fscale[x]: q and the exported b both take the cell's f
+template <bool REG, bool LAW = false>
 __global__ void material_q_kernel(const double *phi, int nparts, const double *B, const double *sigma, double W,
-                                  const double *bpart, double *q, int Gl, int N, const int *cell_region) {
+                                  const double *bpart, double *q, int Gl, int N, const int *cell_region,
+                                  const double *fscale) {
   const int lane = threadIdx.x & 63;
   const int nw = (gridDim.x * blockDim.x) >> 6;
   const size_t NG = static_cast<size_t>(N) * Gl;
@@ -1746,8 +1900,13 @@ __global__ void material_q_kernel(const double *phi, int nparts, const double *B
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if (lane == 0) {
-      q[x] = acc;
-      q[N + x] = bpart[x];  // the exchange buffer's second half: this handle's sum sigma dB/dT
+      if constexpr (LAW) {
+        q[x] = fscale[x] * acc;
+        q[N + x] = fscale[x] * bpart[x];
+      } else {
+        q[x] = acc;
+        q[N + x] = bpart[x];  // the exchange buffer's second half: this handle's sum sigma dB/dT
+      }
     }
   }
 }
@@ -1777,8 +1936,9 @@ __device__ PlanckPair material_emission_all(const PlanckCells &pc, const double 
 // its owed emission grows by B_g(T') - B_g(T) here and dTlast is 0 (no dB/dT dT term).
 // REG: the cell's own heat capacity rho_cv_r[cell_region[x]] (the argument is unused) and, on
 // the Newton path, its own row of the [nregions][G] table of every group's opacity.
+// LAW: S(T') with the cell's lagged opacity, f(x) held fixed during the solve.
 constexpr double kNewtonFrac = 0.25;
-template <bool REG>
+template <bool REG, bool LAW = false>
 __global__ void material_update_kernel(PlanckCells pc, double *T, const double *qb, double *dTlast, double dt,
                                        double rho_cv_one, double W, int N) {
   __shared__ double rk[65];
@@ -1804,7 +1964,12 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
       dTlast[x] = dT;
       continue;
     }
-    const PlanckPair s0 = material_emission_all(pc, sigma_all, T0, rk);
+    PlanckPair s0 = material_emission_all(pc, sigma_all, T0, rk);
+    double f = 1.0;
+    if constexpr (LAW) {
+      f = pc.fscale[x];
+      s0 = PlanckPair{f * s0.b, f * s0.db};
+    }
     const double A = q + W * s0.b;
     const double hi0 = T0 + dt * A / rho_cv;  // f(hi0) = dt W S(hi0) >= 0
     double Tn = hi0;
@@ -1828,10 +1993,11 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
       }
       Tn = t;
       for (int it = 0; it < 200; ++it) {
-        const PlanckPair sv = material_emission_all(pc, sigma_all, t, rk);
-        const double f = rho_cv * (t - T0) + dt * W * sv.b - dt * A;
-        if (f > 0.0) hi = t; else lo = t;
-        double tn = t - f / (rho_cv + dt * W * sv.db);
+        PlanckPair sv = material_emission_all(pc, sigma_all, t, rk);
+        if constexpr (LAW) sv = PlanckPair{f * sv.b, f * sv.db};
+        const double fv = rho_cv * (t - T0) + dt * W * sv.b - dt * A;
+        if (fv > 0.0) hi = t; else lo = t;
+        double tn = t - fv / (rho_cv + dt * W * sv.db);
         if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
         Tn = tn;
         if (fabs(tn - t) <= 1e-15 * fabs(tn) || hi - lo <= 1e-15 * hi) break;
@@ -1853,9 +2019,11 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
 // E[x] = dt W sum_gl sigma_gl ((Beff - B) + owed): the energy per volume the material owes
 // the radiation (rt_get_material_transit); one wave per cell, lanes over groups.  REG: sigma is
 // [nregions][Gl], the cell's region's row
-template <bool REG>
+// LAW: times the cell's fscale[x]
+template <bool REG, bool LAW = false>
 __global__ void material_transit_kernel(const double *B, const double *Beff, const double *owed, const double *sigma,
-                                        double scale, double *E, int Gl, int N, const int *cell_region) {
+                                        double scale, double *E, int Gl, int N, const int *cell_region,
+                                        const double *fscale) {
   const int lane = threadIdx.x & 63;
   const int nw = (gridDim.x * blockDim.x) >> 6;
   for (int x = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; x < N; x += nw) {
@@ -1866,7 +2034,33 @@ __global__ void material_transit_kernel(const double *B, const double *Beff, con
     for (int g = lane; g < Gl; g += 64)
       acc += sg[g] * ((Beff[o + g] - B[o + g]) + owed[static_cast<size_t>(g) * N + x]);
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    if constexpr (LAW) acc *= fscale[x];
     if (lane == 0) E[x] = scale * acc;
+  }
+}
+
+// The opacity law set, changed or cleared between steps (launch_opacity_rescale): the emission
+// in transit of cell x and group gl, (Beff - B) + owed in B units, carries the energy
+// dt W sigma_g f(x) per unit, so it is multiplied by f_old / f_new and paid again by the
+// Planck pass's rule, p = max(owed, -B): Beff = B + p, owed -= p.  One lane per cell.
+__global__ void opacity_rescale_kernel(PlanckCells pc, const double *T, int had_law) {
+  for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < pc.N; x += gridDim.x * blockDim.x) {
+    double f_new = 1.0;
+    if (pc.law_n) {
+      const int rg = pc.cell_region[x];
+      f_new = opacity_scale(T[x], pc.law_Tref[rg], pc.law_n[rg], pc.law_min, pc.law_max);
+    }
+    const double ratio = (had_law ? pc.fscale[x] : 1.0) / f_new;
+    for (int gl = 0; gl < pc.Gl; ++gl) {
+#pragma clang fp contract(off)
+      const size_t o = static_cast<size_t>(gl) * pc.N + x, ob = static_cast<size_t>(x) * pc.Gl + gl;
+      const double b = pc.Bcell[ob];
+      const double owed = (pc.owed[o] + (pc.Beff[ob] - b)) * ratio;
+      const double pay = owed > -b ? owed : -b;
+      pc.owed[o] = owed - pay;
+      pc.Beff[ob] = b + pay;
+    }
+    pc.fscale[x] = f_new;
   }
 }
 
@@ -1956,6 +2150,21 @@ hipError_t launch_walk(int scheme, const SegArgs &a, int grid, hipStream_t st) {
     case SCHEME_BE: hipLaunchKernelGGL(sweep_walk_kernel<SCHEME_BE>, dim3(grid), dim3(64), 0, st, a); break;
     case SCHEME_CN: hipLaunchKernelGGL(sweep_walk_kernel<SCHEME_CN>, dim3(grid), dim3(64), 0, st, a); break;
     default: hipLaunchKernelGGL(sweep_walk_kernel<SCHEME_BDF2>, dim3(grid), dim3(64), 0, st, a); break;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_walk_law(int scheme, const SegArgs &a, const WalkLaw &w, int grid, hipStream_t st) {
+  // the kernel indexes by these: checked here
+  if (!a.bcell || !a.seg_first || !a.seg_region || a.Gl < 1 || a.H < 1 || a.Sg < 1 || a.Q < 1)
+    return hipErrorInvalidValue;
+  if (!w.fscale || !w.rsigma || !w.rdx || !w.mu) return hipErrorInvalidValue;
+  if (a.N < kSweepCells || a.N % kSweepCells || a.N > a.Nrow || a.Lpad != 64 * a.Q) return hipErrorInvalidValue;
+  if (grid != (a.reflective ? a.Q : 2 * a.Q)) return hipErrorInvalidValue;
+  switch (scheme) {
+    case SCHEME_BE: hipLaunchKernelGGL(sweep_walk_law_kernel<SCHEME_BE>, dim3(grid), dim3(64), 0, st, a, w); break;
+    case SCHEME_CN: hipLaunchKernelGGL(sweep_walk_law_kernel<SCHEME_CN>, dim3(grid), dim3(64), 0, st, a, w); break;
+    default: hipLaunchKernelGGL(sweep_walk_law_kernel<SCHEME_BDF2>, dim3(grid), dim3(64), 0, st, a, w); break;
   }
   return hipGetLastError();
 }
@@ -2145,18 +2354,28 @@ hipError_t launch_balance_sums_regions(const double *phi, const double *rk, cons
 }
 
 hipError_t launch_group_absorption_regions(const double *phi, const double *sigma, const int *cell_region,
-                                           double *out, const Geometry &g, hipStream_t st) {
-  hipLaunchKernelGGL(group_absorption_regions_kernel, dim3(grid_for(static_cast<size_t>(g.N), 256)), dim3(256), 0, st,
-                     phi, sigma, cell_region, out, g.Gl, g.N);
+                                           double *out, const Geometry &g, hipStream_t st, const double *fscale) {
+  const dim3 grid(grid_for(static_cast<size_t>(g.N), 256));
+  if (fscale)
+    hipLaunchKernelGGL(group_absorption_regions_kernel<true>, grid, dim3(256), 0, st, phi, sigma, cell_region, out,
+                       g.Gl, g.N, fscale);
+  else
+    hipLaunchKernelGGL(group_absorption_regions_kernel<false>, grid, dim3(256), 0, st, phi, sigma, cell_region, out,
+                       g.Gl, g.N, fscale);
   return hipGetLastError();
 }
 
 hipError_t launch_planck_cells(const PlanckCells &pc, const double *T, double *B, hipStream_t st) {
   const dim3 grid(grid_for(static_cast<size_t>(pc.N), kPlanckCells));
-  if (pc.cell_region)
+  if (pc.fscale && !(pc.cell_region && pc.law_n && pc.law_Tref && pc.fratio)) return hipErrorInvalidValue;
+  if (pc.fscale) {
+    hipLaunchKernelGGL(opacity_scale_kernel, dim3(grid_for(static_cast<size_t>(pc.N), 256)), dim3(256), 0, st, pc, T);
+    hipLaunchKernelGGL((planck_cells_kernel<true, true>), grid, dim3(256), 0, st, pc, T, B);
+  } else if (pc.cell_region) {
     hipLaunchKernelGGL(planck_cells_kernel<true>, grid, dim3(256), 0, st, pc, T, B);
-  else
+  } else {
     hipLaunchKernelGGL(planck_cells_kernel<false>, grid, dim3(256), 0, st, pc, T, B);
+  }
   return hipGetLastError();
 }
 
@@ -2227,21 +2446,30 @@ hipError_t launch_phi_correction_rows(int scheme, const SegArgs &a, const double
 }
 
 hipError_t launch_material_q(const double *phi, int nparts, const double *B, const double *sigma, double W,
-                             const double *bpart, double *q, int Gl, int N, hipStream_t st, const int *cell_region) {
+                             const double *bpart, double *q, int Gl, int N, hipStream_t st, const int *cell_region,
+                             const double *fscale) {
   const dim3 grid(grid_for(static_cast<size_t>(N) * 64, 256));
-  if (cell_region)
+  if (fscale && !cell_region) return hipErrorInvalidValue;  // the law is a region handle's
+  if (fscale)
+    hipLaunchKernelGGL((material_q_kernel<true, true>), grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart, q, Gl,
+                       N, cell_region, fscale);
+  else if (cell_region)
     hipLaunchKernelGGL(material_q_kernel<true>, grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart, q, Gl, N,
-                       cell_region);
+                       cell_region, fscale);
   else
     hipLaunchKernelGGL(material_q_kernel<false>, grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart, q, Gl, N,
-                       cell_region);
+                       cell_region, fscale);
   return hipGetLastError();
 }
 
 hipError_t launch_material_update(const PlanckCells &pc, double *T, const double *qb, double *dTlast, double dt,
                                   double rho_cv, double W, int N, hipStream_t st) {
   const dim3 grid(grid_for(static_cast<size_t>(N), 256));
-  if (pc.cell_region)
+  if (pc.fscale && !pc.cell_region) return hipErrorInvalidValue;
+  if (pc.fscale)
+    hipLaunchKernelGGL((material_update_kernel<true, true>), grid, dim3(256), 0, st, pc, T, qb, dTlast, dt, rho_cv, W,
+                       N);
+  else if (pc.cell_region)
     hipLaunchKernelGGL(material_update_kernel<true>, grid, dim3(256), 0, st, pc, T, qb, dTlast, dt, rho_cv, W, N);
   else
     hipLaunchKernelGGL(material_update_kernel<false>, grid, dim3(256), 0, st, pc, T, qb, dTlast, dt, rho_cv, W, N);
@@ -2249,14 +2477,26 @@ hipError_t launch_material_update(const PlanckCells &pc, double *T, const double
 }
 
 hipError_t launch_material_transit(const double *B, const double *Beff, const double *owed, const double *sigma,
-                                   double scale, double *E, int Gl, int N, hipStream_t st, const int *cell_region) {
+                                   double scale, double *E, int Gl, int N, hipStream_t st, const int *cell_region,
+                                   const double *fscale) {
   const dim3 grid(grid_for(static_cast<size_t>(N) * 64, 256));
-  if (cell_region)
+  if (fscale && !cell_region) return hipErrorInvalidValue;
+  if (fscale)
+    hipLaunchKernelGGL((material_transit_kernel<true, true>), grid, dim3(256), 0, st, B, Beff, owed, sigma, scale, E,
+                       Gl, N, cell_region, fscale);
+  else if (cell_region)
     hipLaunchKernelGGL(material_transit_kernel<true>, grid, dim3(256), 0, st, B, Beff, owed, sigma, scale, E, Gl, N,
-                       cell_region);
+                       cell_region, fscale);
   else
     hipLaunchKernelGGL(material_transit_kernel<false>, grid, dim3(256), 0, st, B, Beff, owed, sigma, scale, E, Gl, N,
-                       cell_region);
+                       cell_region, fscale);
+  return hipGetLastError();
+}
+
+hipError_t launch_opacity_rescale(const PlanckCells &pc, const double *T, int had_law, hipStream_t st) {
+  if (!pc.fscale || !pc.cell_region || !pc.Bcell || (pc.law_n && !pc.law_Tref)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(opacity_rescale_kernel, dim3(grid_for(static_cast<size_t>(pc.N), 256)), dim3(256), 0, st, pc, T,
+                     had_law);
   return hipGetLastError();
 }
 

@@ -102,6 +102,16 @@ hipError_t launch_sweep(int scheme, int T, int mode, const SegArgs &a, int grid,
 // with the unit-B maps (one set per region), bcell, Gl, H, seg_first and seg_region; N and every
 // segment edge multiples of 16; grid = 2 Q, or Q with the reflective left boundary
 hipError_t launch_walk(int scheme, const SegArgs &a, int grid, hipStream_t st);
+// ... with the opacity law on (sweep_walk_law_kernel): no map; each lane forms its cell's line
+// constants from sigma(x) = sigma0[region][group] f(x) and runs the reference algebra (cell.hpp)
+struct WalkLaw {
+  const double *fscale;       // [N] the law's scale f(x) of every cell (physical cell order)
+  const double *rsigma;       // [nregions][Gl] rho kappa of the handle's groups, unscaled
+  const double *rdx;          // [nregions] cell width
+  const double *mu;           // [M] direction cosines
+  double c, tau, dt;          // speed of light, the substep (dt / 2 for BDF2), the step
+};
+hipError_t launch_walk_law(int scheme, const SegArgs &a, const WalkLaw &w, int grid, hipStream_t st);
 // the level-split pipelined BDF2 pass (kernels_split.hip): T levels over `waves` waves
 hipError_t launch_split(int T, int waves, const SegArgs &a, int grid, hipStream_t st);
 hipError_t split_occupancy(int T, int waves, int *workgroups_per_cu);
@@ -150,7 +160,8 @@ hipError_t launch_balance_sums_regions(const double *phi, const double *rk, cons
                                        const int *cell_region, double *part, double *ab, double *sr, int Gl, int N,
                                        hipStream_t st);
 hipError_t launch_group_absorption_regions(const double *phi, const double *sigma, const int *cell_region,
-                                           double *out, const Geometry &g, hipStream_t st);
+                                           double *out, const Geometry &g, hipStream_t st,
+                                           const double *fscale = nullptr);  // the opacity law's f(x)
 
 // Planck group integrals per cell (material coupling): the algorithm of
 // Planck.cpp:44-337 in double precision on the device.
@@ -179,6 +190,14 @@ struct PlanckCells {
   const double *rsigma;         // [nregions][Gl] rho kappa of the handle's groups
   const double *rsigma_all;     // [nregions][G] rho kappa of every group
   const double *rho_cv_r;       // [nregions] heat capacity
+  // the opacity law (rt_material_set_opacity_law; region handles only): sigma_g(x) = rsigma f(x),
+  // f = clamp((T / law_Tref)^(-law_n), law_min, law_max) per cell.  nullptr: off (the kernels'
+  // other forms, untouched)
+  double *fscale;               // [N] f(x): read as f_old, written as f_new by the Planck pass
+  double *fratio;               // [N] f_old / f_new of that pass (scratch of the pass)
+  const double *law_n;          // [nregions] exponent
+  const double *law_Tref;       // [nregions] reference temperature
+  double law_min, law_max;
 };
 // B[N][Gl] = B_g(T(x)) and the fields above
 hipError_t launch_planck_cells(const PlanckCells &pc, const double *T, double *B, hipStream_t st);
@@ -202,9 +221,10 @@ hipError_t launch_correction_power(int scheme, const double *map, double *pow, i
 // q[x] = sum_g sigma_g (phi_g(x) - W B_g(x)) over the handle's groups, phi the
 // sum of nparts [N][Gl] arrays at phi (the fused parts, or one full phi); q[N + x] = bpart[x].
 // cell_region: sigma is [nregions][Gl] and cell x takes the row cell_region[x]
+// fscale (region form only): the opacity law's f(x) scales both q and b of cell x
 hipError_t launch_material_q(const double *phi, int nparts, const double *B, const double *sigma, double W,
                              const double *bpart, double *q, int Gl, int N, hipStream_t st,
-                             const int *cell_region = nullptr);
+                             const int *cell_region = nullptr, const double *fscale = nullptr);
 // from qb = [q, b] summed over all groups: dT = dt q / (rho_cv + dt W b), T(x) += dT, dTlast = dT
 // T += dt q / (rho_cv + dt W b), or the root of the full emission where dT > T / 4 (its owed
 // emission added there, dT 0): rt_oracle.c orc_material_update.  pc.cell_region set: rho_cv is
@@ -215,6 +235,11 @@ hipError_t launch_material_update(const PlanckCells &pc, double *T, const double
 // cell_region: as for launch_material_q
 hipError_t launch_material_transit(const double *B, const double *Beff, const double *owed, const double *sigma,
                                    double scale, double *E, int Gl, int N, hipStream_t st,
-                                   const int *cell_region = nullptr);
+                                   const int *cell_region = nullptr, const double *fscale = nullptr);
+// the opacity law set, changed or cleared between steps: f_new from T (pc.fscale then holds it;
+// pc.law_n == nullptr: 1), and the emission in transit (Beff - B) + owed of every cell and group
+// times f_old / f_new, paid again as p = max(owed, -B): Beff = B + p, owed -= p.  f_old: pc.fscale,
+// or 1 where had_law is 0
+hipError_t launch_opacity_rescale(const PlanckCells &pc, const double *T, int had_law, hipStream_t st);
 
 }  // namespace rtamd

@@ -278,6 +278,13 @@ struct rt_solver {
   // every group [regions][G] back to back; map_unit then holds one unit-B map set per region
   rtsn_detail::DeviceBuf rmaterial;
   std::vector<double> rho_cv_r;  // [regions] heat capacities (host copy: rt_material_stability)
+  // the opacity law (rt_material_set_opacity_law; a coupled region handle in segment mode):
+  // sigma_g(x) = rho kappa_g f(x).  fscale [N] the cells' f, lagged: formed from T^n by the Planck
+  // pass; lawtab [2][regions] exponent, T_ref (device), law_n / law_Tref their host copies
+  bool law = false;
+  std::vector<double> law_n, law_Tref;
+  double law_min = 1.0, law_max = 1.0;
+  rtsn_detail::DeviceBuf fscale, lawtab;
   long long lane_off[4] = {-1, -1, -1, -1};
   // segment mode (long lines): the pipelined segment pass with every segment inside one region
   // (regions::plan_segments at the target Ls of segment_lines); seg_tab the kernel's tables

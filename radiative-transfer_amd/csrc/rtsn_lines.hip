@@ -34,43 +34,15 @@ static LineConstT<long double> line_constants(const rt_solver &s, int i, int g, 
   const real tau = (p.ts_method == 3) ? dt / real(2.0) : dt;
   const real mu = s.mu[i], m = std::fabs(mu);
   const real sigma = real(gt.rho[g]) * gt.kappa[g];
-  LineConstT<real> L{};
+  // the cell systems and the unit source (cell.hpp: the definition the law walk shares)
+  LineConstT<real> L = line_constants_unit<real>(c, tau, dt, m, sigma, real(dx));
   const real half = real(0.5) * c * tau * dx;
   // S = 1/2 c tau dx (sigma B_g + total_correction), psi = (e_in + e_out)/2
-  L.c[LC_SC] = half * sigma * (unit_B ? real(1.0) : gt.B[g]);
-  L.c[LC_SL] = real(0.0);
+  if (!unit_B) L.c[LC_SC] *= real(gt.B[g]);
   if (p.use_correction) {
     const real beta = p.V / c;
     L.c[LC_SC] += half * ((gt.cor2[g] * mu) * beta - gt.cor3[g] * (mu * mu) * (beta * beta));
     L.c[LC_SL] = half * gt.cor1[g] * mu * beta * real(0.5);
-  }
-  auto inverse = [](real d, real o, real &i0, real &i1) {
-    const real det = d * d + o * o;
-    i0 = d / det;
-    i1 = o / det;
-  };
-  {  // BE(tau)
-    const real a = real(1.0) + c * tau * sigma, b = c * tau * m;
-    L.c[LC_BE_B] = b;
-    inverse((a * dx + b) / real(2.0), b / real(2.0), L.c[LC_BE_I0], L.c[LC_BE_I1]);
-  }
-  {  // CN(tau)
-    const real t = real(0.5) * c * tau * sigma, A = real(0.5) * c * m * tau;
-    const real Bp = real(1.0) + t, Cp = real(1.0) - t;
-    L.c[LC_CN_A] = A;
-    L.c[LC_CN_K1] = real(0.5) * (Cp * dx - A);
-    L.c[LC_CN_K2] = real(0.5) * A;
-    inverse(real(0.5) * (A + Bp * dx), A / real(2.0), L.c[LC_CN_I0], L.c[LC_CN_I1]);
-  }
-  {  // BDF(tau) with const_B from the full dt
-    const real t = c * sigma * tau / real(6.0), Ab = real(1.0) + t, Bc = c * m * dt / real(6.0);
-    const real Cb = real(1.0) - real(4.0) * t, D = t;
-    L.c[LC_BD_BC] = Bc;
-    L.c[LC_BD_Q1] = real(0.5) * (Cb * dx - real(4.0) * Bc);
-    L.c[LC_BD_Q2] = real(2.0) * Bc;
-    L.c[LC_BD_Q3] = real(0.5) * (Bc + D * dx);
-    L.c[LC_BD_Q4] = real(0.5) * Bc;
-    inverse(real(0.5) * (Ab * dx + Bc), real(0.5) * Bc, L.c[LC_BD_I0], L.c[LC_BD_I1]);
   }
   return L;
 }

@@ -1,6 +1,7 @@
 // rtsn_material.hip -- material-temperature coupling (include/rtsn.h "material"):
 // per-cell Planck emission and its T derivative, the coupled sweep with fused angular sums,
-// the T update implicit in the material's own emission and the owed emission it implies.
+// the T update implicit in the material's own emission and the owed emission it implies; on a
+// coupled region handle in segment mode, the temperature-dependent opacity (the opacity law).
 
 #include "rtsn_internal.hpp"
 
@@ -38,6 +39,14 @@ static double material_stability_number(const rt_solver *s, const phys::GroupTab
   return s->p.dt * W * sum / rho_cv;
 }
 
+// the opacity law's scale of region k at temperature T (the device's opacity_scale, kernels.hip)
+static double opacity_scale_host(const rt_solver *s, int k, double T) {
+  const double n = s->law_n[k];
+  const double v = T > 0.0 && std::isfinite(T) ? std::pow(T / s->law_Tref[k], -n)
+                                               : (n > 0.0 ? s->law_max : (n < 0.0 ? s->law_min : 1.0));
+  return std::min(std::max(v, s->law_min), s->law_max);
+}
+
 extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
   if (!s || !number) return fail(s, RT_ERR_ARG, "rt_material_stability: bad argument");
   if (!s->material) return fail(s, RT_ERR_STATE, "rt_material_stability: material coupling is off");
@@ -51,7 +60,9 @@ extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
       double T_max = 0.0;
       for (int c = s->first_cell[k]; c < s->first_cell[k + 1]; ++c)
         if (std::isfinite(T[c])) T_max = std::max(T_max, T[c]);
-      worst = std::max(worst, material_stability_number(s, s->regions[k].gt, s->rho_cv_r[k], T_max));
+      double number = material_stability_number(s, s->regions[k].gt, s->rho_cv_r[k], T_max);
+      if (s->law) number *= opacity_scale_host(s, static_cast<int>(k), T_max);  // the opacity there
+      worst = std::max(worst, number);
     }
     *number = worst;
     return RT_OK;
@@ -167,6 +178,9 @@ static rt_status enable_region_coupling(rt_solver *s, const double *rho_cv, cons
   pc.rsigma_all = pc.rho_cv_r + R;
   s->rho_cv_r.assign(rho_cv, rho_cv + R);
   s->rho_cv = rho_cv[0];
+  s->law = false;  // (enabled again: the opacity law is off until set)
+  pc.fscale = nullptr;
+  pc.law_n = pc.law_Tref = nullptr;
   if ((st = material_planck(s))) return st;
   HIP_TRY(s, hipStreamSynchronize(s->stream));  // T0 dies at return
   s->material = true;  // from here the chain is the one-step plan's (region_wave_plan)
@@ -287,7 +301,8 @@ extern "C" rt_status rt_material_sweep(rt_solver *s, double *d_q) {
     if ((st = s->seg_mode ? walk_coupled_pass(s) : wave_coupled_pass(s))) return st;
     if ((st = compute_moments(s))) return st;
     HIP_TRY(s, launch_material_q(static_cast<const double *>(s->mom.p), 1, B, static_cast<const double *>(s->rmedium.p),
-                                 s->wsum, bp, q, s->Gl, s->p.N, s->stream, static_cast<const int *>(s->cell_region.p)));
+                                 s->wsum, bp, q, s->Gl, s->p.N, s->stream, static_cast<const int *>(s->cell_region.p),
+                                 s->law ? static_cast<const double *>(s->fscale.p) : nullptr));
     return RT_OK;
   }
   if (s->phi_fused) {
@@ -408,11 +423,87 @@ extern "C" rt_status rt_get_material_transit(rt_solver *s, double *E) {
       static_cast<const double *>(s->Bcell.p), static_cast<const double *>(s->Beff.p),
       static_cast<const double *>(s->owed.p), static_cast<const double *>(regional(s) ? s->rmedium.p : s->sigma.p),
       s->p.dt * s->wsum, static_cast<double *>(d.p), s->Gl, s->p.N, s->stream,
-      regional(s) ? static_cast<const int *>(s->cell_region.p) : nullptr);
+      regional(s) ? static_cast<const int *>(s->cell_region.p) : nullptr,
+      s->law ? static_cast<const double *>(s->fscale.p) : nullptr);
   if (e == hipSuccess) e = hipMemcpyAsync(E, d.p, sizeof(double) * s->p.N, hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   (void)hipStreamSynchronize(s->stream);
   d.reset();
   if (e != hipSuccess) return fail(s, RT_ERR_DEVICE, std::string("rt_get_material_transit: ") + hipGetErrorString(e));
+  return RT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the opacity law (include/rtsn.h rt_material_set_opacity_law)
+// ---------------------------------------------------------------------------
+extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exponent, const double *T_ref,
+                                                 int nregions, double scale_min, double scale_max) {
+  const char *fn = "rt_material_set_opacity_law";
+  if (!s) return fail(nullptr, RT_ERR_ARG, std::string(fn) + ": NULL handle");
+  if (!regional(s))
+    return fail(s, RT_ERR_STATE, std::string(fn) + ": not a region handle; the law needs a region handle in segment "
+                                 "mode (rt_create_regions, rt_set_wavefront(s, 0), rt_material_enable_segments)");
+  if (!s->seg_mode)
+    return fail(s, RT_ERR_STATE, std::string(fn) + ": the handle is in chain mode; the law runs on the line walk of "
+                                 "segment mode (rt_set_wavefront(s, 0), then rt_material_enable_segments)");
+  if (!s->material)
+    return fail(s, RT_ERR_STATE, std::string(fn) + ": call rt_material_enable_segments first");
+  const int R = static_cast<int>(s->regions.size());
+  const bool off = !exponent && nregions == 0;
+  if (!off) {
+    if (!exponent || !T_ref) return fail(s, RT_ERR_ARG, std::string(fn) + ": NULL exponent or T_ref");
+    if (nregions != R)
+      return fail(s, RT_ERR_ARG, std::string(fn) + ": nregions must be the handle's " + std::to_string(R));
+    for (int k = 0; k < R; ++k) {
+      if (!std::isfinite(exponent[k])) return fail(s, RT_ERR_ARG, std::string(fn) + ": every exponent must be finite");
+      if (!(T_ref[k] > 0.0) || !std::isfinite(T_ref[k]))
+        return fail(s, RT_ERR_ARG, std::string(fn) + ": every T_ref must be finite and > 0");
+    }
+    if (!(scale_min > 0.0) || !(scale_min <= scale_max) || !std::isfinite(scale_max))
+      return fail(s, RT_ERR_ARG, std::string(fn) + ": need 0 < scale_min <= scale_max < infinity");
+  }
+  if (off && !s->law) return RT_OK;
+  HIP_TRY(s, hipSetDevice(s->device));
+  const size_t N = s->p.N;
+  if (!s->fscale.p) {
+    hipError_t e = dalloc(s->fscale, sizeof(double) * 2 * N);  // f, then the Planck pass's f_old / f_new
+    if (!e) e = dalloc(s->lawtab, sizeof(double) * 2 * R);
+    if (e) return fail(s, RT_ERR_NOMEM, std::string("opacity law buffers: ") + hipGetErrorString(e));
+  }
+  PlanckCells &pc = s->pc;
+  const int had_law = s->law ? 1 : 0;
+  if (!off) {
+    std::vector<double> tab(2 * R);
+    std::copy(exponent, exponent + R, tab.begin());
+    std::copy(T_ref, T_ref + R, tab.begin() + R);
+    if (rt_status st = upload(s, s->lawtab, tab.data(), tab.size() * sizeof(double))) return st;
+    s->law_n.assign(exponent, exponent + R);
+    s->law_Tref.assign(T_ref, T_ref + R);
+    s->law_min = pc.law_min = scale_min;
+    s->law_max = pc.law_max = scale_max;
+    pc.law_n = static_cast<const double *>(s->lawtab.p);
+    pc.law_Tref = pc.law_n + R;
+  } else {
+    pc.law_n = pc.law_Tref = nullptr;
+  }
+  pc.fscale = static_cast<double *>(s->fscale.p);
+  pc.fratio = pc.fscale + N;
+  // f from the current T, and the emission in transit rescaled by f_old / f_new (off: f_new = 1)
+  HIP_TRY(s, launch_opacity_rescale(pc, static_cast<const double *>(s->Tcell.p), had_law, s->stream));
+  s->law = !off;
+  if (off) pc.fscale = nullptr;  // the kernels' forms without the law again
+  return RT_OK;
+}
+
+extern "C" rt_status rt_get_opacity_scale(rt_solver *s, double *f) {
+  if (!s || !f) return fail(s, RT_ERR_ARG, "rt_get_opacity_scale: bad argument");
+  if (!s->material) return fail(s, RT_ERR_STATE, "rt_get_opacity_scale: material coupling is off");
+  if (!s->law) {  // no law: the table opacities
+    std::fill(f, f + s->p.N, 1.0);
+    return RT_OK;
+  }
+  HIP_TRY(s, hipSetDevice(s->device));
+  HIP_TRY(s, hipMemcpyAsync(f, s->fscale.p, sizeof(double) * s->p.N, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
   return RT_OK;
 }

@@ -445,7 +445,8 @@ extern "C" rt_status rt_group_absorption_device(rt_solver *s, double *d_out) {
     HIP_TRY(s, launch_group_absorption_regions(static_cast<const double *>(s->mom.p),
                                                static_cast<const double *>(s->rmedium.p),
                                                static_cast<const int *>(s->cell_region.p), d_out, geometry(s),
-                                               s->stream));
+                                               s->stream,
+                                               s->law ? static_cast<const double *>(s->fscale.p) : nullptr));
   else
     HIP_TRY(s, launch_group_absorption(static_cast<const double *>(s->mom.p), static_cast<const double *>(s->sigma.p),
                                        d_out, geometry(s), s->stream));

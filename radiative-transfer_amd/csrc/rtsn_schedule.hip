@@ -533,7 +533,21 @@ rt_status rtsn_detail::walk_coupled_pass(rt_solver *s) {
   hipEvent_t e1;
   rt_status st = event_begin(s, &e1);
   if (st) return st;
-  const hipError_t e = launch_walk(s->scheme, a, (a.reflective ? 1 : 2) * s->Q, s->stream);
+  hipError_t e;
+  if (s->law) {  // the opacity law: the constants formed per cell from sigma0 f(x), no map
+    const size_t R = s->regions.size();
+    WalkLaw w{};
+    w.fscale = static_cast<const double *>(s->fscale.p);
+    w.rsigma = static_cast<const double *>(s->rmedium.p);
+    w.rdx = w.rsigma + 2 * R * s->Gl;  // rmedium: rho kappa and the balance's emission [regions][Gl], then dx
+    w.mu = static_cast<const double *>(s->muwt.p);
+    w.c = phys::kLight;
+    w.dt = s->p.dt;
+    w.tau = s->p.ts_method == 3 ? s->p.dt / 2.0 : s->p.dt;
+    e = launch_walk_law(s->scheme, a, w, (a.reflective ? 1 : 2) * s->Q, s->stream);
+  } else {
+    e = launch_walk(s->scheme, a, (a.reflective ? 1 : 2) * s->Q, s->stream);
+  }
   if (e != hipSuccess) {
     event_abort(s, e1);
     return fail(s, RT_ERR_DEVICE, std::string("coupled walk launch: ") + hipGetErrorString(e));

@@ -153,6 +153,8 @@ def lib():
         L.rt_material_enable.argtypes = [vp, C.c_double, dp]
         L.rt_material_enable_regions.argtypes = [vp, dp, C.c_int, dp]
         L.rt_material_enable_segments.argtypes = [vp, dp, C.c_int, dp]
+        L.rt_material_set_opacity_law.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.c_double]
+        L.rt_get_opacity_scale.argtypes = [vp, dp]
         L.rt_material_sweep.argtypes = [vp, vp]
         L.rt_material_update.argtypes = [vp, vp]
         L.rt_material_step.argtypes = [vp, C.c_int]
@@ -620,6 +622,27 @@ class Solver:
         _check(lib().rt_material_enable_segments(self._h, _dp(rc), int(rc.size), None if T is None else _dp(T)),
                "rt_material_enable_segments", self._h)
         return self.material_stability()
+
+    def material_set_opacity_law(self, exponent, T_ref, scale_min: float, scale_max: float):
+        """sigma_g(x) = rho kappa_g f(x), f = clamp((T / T_ref[k])^(-exponent[k]), scale_min,
+        scale_max) per cell of region k (rt_material_set_opacity_law): a coupled region handle in
+        segment mode; the opacity is lagged (f from T^n).  exponent None: the law off."""
+        if exponent is None:
+            _check(lib().rt_material_set_opacity_law(self._h, None, None, 0, float(scale_min), float(scale_max)),
+                   "rt_material_set_opacity_law", self._h)
+            return
+        n = np.ascontiguousarray(exponent, dtype=np.float64).ravel()
+        tr = np.ascontiguousarray(T_ref, dtype=np.float64).ravel()
+        if tr.size != n.size:
+            raise ValueError("material_set_opacity_law: one exponent and one T_ref per region")
+        _check(lib().rt_material_set_opacity_law(self._h, _dp(n), _dp(tr), int(n.size), float(scale_min),
+                                                 float(scale_max)), "rt_material_set_opacity_law", self._h)
+
+    def opacity_scale(self) -> np.ndarray:
+        """(N) the opacity law's f(x) as the next coupled step uses it (1 with the law off)."""
+        out = np.empty(self.N)
+        _check(lib().rt_get_opacity_scale(self._h, _dp(out)), "rt_get_opacity_scale", self._h)
+        return out
 
     def material_stability(self) -> float:
         """dt W sum_g rho kappa_g dB_g/dT(T_max) / rho_cv: the emission's stiffness at the hottest
