@@ -427,8 +427,42 @@ rt_status rt_material_enable_segments(rt_solver *s, const double *rho_cv, int nr
  * do not satisfy 0 < scale_min <= scale_max < infinity. */
 rt_status rt_material_set_opacity_law(rt_solver *s, const double *exponent, const double *T_ref, int nregions,
                                       double scale_min, double scale_max);
-/* f(x) of every cell (N, host) as the next step will use it; 1 with the law off. */
+/* f(x) of every cell (N, host) as the next step will use it; 1 with the law off.  RT_ERR_STATE
+ * with the opacity table on (one f per cell and group: rt_get_opacity_scale_groups). */
 rt_status rt_get_opacity_scale(rt_solver *s, double *f);
+/* Tabulated per-group opacities kappa_g(T) on the same handles, with the law's preconditions,
+ * statuses and messages: region k's cells take sigma_g(x) = rho_k kappa_{k,g} f_{k,g}(T(x)), f
+ * given at the nT nodes of T_grid (strictly increasing, finite, > 0, nT >= 2) as
+ * scale[nregions][nT][G] over ALL G groups of the configuration, not the shard's (the Newton
+ * path's S(T') sums every group on every rank); every entry finite and > 0.  T_grid == NULL with
+ * nT == 0 and nregions == 0 turns the table off.
+ * Between nodes f is linear in (ln T, ln f), outside the grid constant: with j the bracket of T,
+ *   t = log(T / T_j) r_j,   r_j = 1 / log(T_{j+1} / T_j),
+ *   ln f = fma(t, ln f_{j+1} - ln f_j, ln f_j),   f = exp(ln f);
+ * T below the first node, T <= 0 or T not finite (the law's 0+ rule) takes the first node's
+ * value exp(ln f_0), T at or above the last node the last node's.  r_j and the logs of the table
+ * are formed on the host in long double, rounded once and uploaded; log and exp run in fp64 on
+ * the device.  A clamped power law is such a table (linear in log-log with constant ends), so
+ * per-group exponents need no interface of their own.
+ * Lagging and conservation are the law's, per group: f_g comes from T^n when the table is set
+ * and after every update, and the finalised owed emission of group g is multiplied by
+ * f_old,g / f_new,g before the payment is taken; setting, changing or clearing the table in
+ * mid-run rescales the emission in transit per group and pays it again.  The sweep, q, b (the
+ * factor inside its sum), the S(T') of the Newton path, rt_get_material_transit,
+ * rt_material_stability (f_g at each region's hottest cell) and rt_group_absorption_device all
+ * take sigma_g f_g.
+ * The table and the law exclude each other: setting one while the other is on replaces it through
+ * the same rescale (f_old is whichever was in force, 1 if neither); turning off the one that is
+ * not on leaves the other in force.  Set and cleared before any step, the handle is bitwise as
+ * before.
+ * RT_ERR_ARG: nregions not the handle's, nT < 2, a grid that is not increasing, not positive or
+ * not finite, a scale entry that is not finite or <= 0, NULL arrays when not turning it off. */
+rt_status rt_material_set_opacity_table(rt_solver *s, const double *T_grid, int nT, const double *scale,
+                                        int nregions);
+/* f_g(x) of every cell and each of the handle's groups (N x G_local, host, f[g + G_local * c]) as
+ * the next step will use it, in every state: 1 with nothing set, the law's f(x) repeated over the
+ * groups, the table's f_g(x). */
+rt_status rt_get_opacity_scale_groups(rt_solver *s, double *f);
 /* The emission's stiffness at the current T(x): number = dt W sum_g rho kappa_g
  * dB_g/dT(T_max) / rho_cv over ALL G groups (a shard reports the whole configuration's
  * number); the implicit update scales the explicit change by 1 / (1 + number) at the

@@ -592,6 +592,9 @@ __global__ __launch_bounds__(64) void sweep_walk_kernel(SegArgs a) {
 // rows with the rows, the emission scale and f(x) (wave-uniform per row) prefetched across
 // segment edges, the carried state in registers; sigma0 and dx are reloaded at a segment's first
 // chunk, where that kernel reloads the map.
+// TAB (the opacity table, rt_material_set_opacity_table): f is per group, so the row's f is no
+// longer wave-uniform: a lane loads f of (cell, its group) from the cell-major [N][G] table, as
+// bload does the emission, and prefetches it with bv.  Nothing else of the walk changes.
 // One chunk: LAST -- no prefetch.  head: the chunk's first cell is the reflective head cell.
 template <int S, int C, bool LAST, typename BL, typename FL>
 __device__ __forceinline__ void walk_law_chunk(const WalkLaw &w, double m, double sig0, double dx, bool neg,
@@ -621,7 +624,7 @@ __device__ __forceinline__ void walk_law_chunk(const WalkLaw &w, double m, doubl
   }
 }
 
-template <int S>
+template <int S, bool TAB = false>
 __global__ __launch_bounds__(64) void sweep_walk_law_kernel(SegArgs a, WalkLaw w) {
   constexpr int K = SchemeDim<S>::K;
   constexpr int C = kSweepCells;
@@ -635,6 +638,8 @@ __global__ __launch_bounds__(64) void sweep_walk_law_kernel(SegArgs a, WalkLaw w
   const int voff = lane * static_cast<int>(sizeof(double2));
   const int gl = min(ell / a.H, a.Gl - 1), ip = ell % a.H;  // padding lanes: a clamped, unused group
   const double *bl = a.bcell + gl;
+  const double *fl = w.fscale;
+  if constexpr (TAB) fl = w.fscale + w.fgroup0 + gl;  // the lane's column of the [N][G] table
   double X[K];
   {
     const double v = a.bdry[static_cast<size_t>(h0) * stride + ell];
@@ -664,7 +669,10 @@ __global__ __launch_bounds__(64) void sweep_walk_law_kernel(SegArgs a, WalkLaw w
       return static_cast<size_t>(neg ? a.N - 1 - kk : kk);
     };
     auto bload = [&](int k) -> double { return bl[cell_of(k) * a.Gl]; };
-    auto fload = [&](int k) -> double { return w.fscale[cell_of(k)]; };
+    auto fload = [&](int k) -> double {
+      if constexpr (TAB) return fl[cell_of(k) * w.fstride];
+      else return w.fscale[cell_of(k)];
+    };
     double ein[C], eout[C], bv[C], fv[C];
     {
       const __amdgpu_buffer_rsrc_t R0 = rows(0);
@@ -1135,13 +1143,20 @@ __global__ void balance_partials_regions_kernel(const double *phi, const double 
   part[(static_cast<size_t>(rp) * Gl + g) * 2 + 1] = e;
 }
 
-template <bool LAW = false>  // LAW: times the opacity law's fscale[c]
+// LAW: times the opacity law's fscale[c].  TAB (the opacity table): sigma_g f_g(c) inside the sum,
+// f_g(c) = fscale[c fstride + g]
+template <bool LAW = false, bool TAB = false>
 __global__ void group_absorption_regions_kernel(const double *phi, const double *sigma, const int *cell_region,
-                                                double *out, int Gl, int N, const double *fscale) {
+                                                double *out, int Gl, int N, const double *fscale, int fstride) {
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < N; c += gridDim.x * blockDim.x) {
     const double *sg = sigma + static_cast<size_t>(cell_region[c]) * Gl;
     double s = 0.0;
-    for (int g = 0; g < Gl; ++g) s += sg[g] * phi[static_cast<size_t>(c) * Gl + g];
+    if constexpr (TAB) {
+      const double *fg = fscale + static_cast<size_t>(c) * fstride;
+      for (int g = 0; g < Gl; ++g) s += (sg[g] * fg[g]) * phi[static_cast<size_t>(c) * Gl + g];
+    } else {
+      for (int g = 0; g < Gl; ++g) s += sg[g] * phi[static_cast<size_t>(c) * Gl + g];
+    }
     if constexpr (LAW) s *= fscale[c];
     out[c] = s;
   }
@@ -1317,10 +1332,55 @@ __global__ void opacity_scale_kernel(PlanckCells pc, const double *T) {
   }
 }
 
+// TAB (REG only, not with LAW; the opacity table, PlanckCells.ftab set): sigma_gl(x) = rsigma
+// f_gl(x), one f per cell and group.  opacity_table_kernel, launched ahead of the pass where
+// opacity_scale_kernel is for the law, keeps exp and log out of this kernel: one wave per cell
+// finds the bracket j of T(x) and t = log(T / T_j) r_j once (wave-uniform), then its lanes take
+// the groups in steps of 64: ln f = fma(t, ln f_{j+1} - ln f_j, ln f_j), f = exp(ln f), for ALL G
+// groups (the update's S(T') sums every group on every rank) to ftab[x][g], cell-major like Bcell,
+// and f_old / f_new of the handle's own groups to gratio[gl][x], group-major like owed.  T below
+// the first node, T <= 0 or not finite: t = 0 at the first node; T at or above the last node:
+// t = 0 at the last -- fma(0, d, a) is a, so a node's value is exp(ln f_j) on either side of it.
+// had: what f_old is -- kOpacityTable ftab as the last pass left it, kOpacityLaw fscale[x],
+// kOpacityNone 1 (the last two when the table is set in mid-run, launch_opacity_rescale).
+// The owed rescale is then per (group, cell), and bpart = sum sigma_g f_g dB_g/dT with the factor
+// inside the sum: it no longer factors out, and material_q_kernel exports bpart as it is.
+__global__ void opacity_table_kernel(PlanckCells pc, const double *T, int had) {
+  const int lane = threadIdx.x & 63;
+  const int nw = (gridDim.x * blockDim.x) >> 6;
+  const int nT = pc.tab_nT, G = pc.G;
+  for (int x = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; x < pc.N; x += nw) {  // wave-uniform
+    const double Tx = T[x];
+    int j = 0;
+    double t = 0.0;
+    if (Tx > 0.0 && isfinite(Tx) && Tx >= pc.tab_T[0]) {
+      if (Tx >= pc.tab_T[nT - 1]) {
+        j = nT - 1;
+      } else {
+        while (j + 2 < nT && Tx >= pc.tab_T[j + 1]) ++j;
+        t = log(Tx / pc.tab_T[j]) * pc.tab_r[j];
+      }
+    }
+    const double *l0 = pc.tab_lnf + (static_cast<size_t>(pc.cell_region[x]) * nT + j) * G;
+    const double *l1 = j + 1 < nT ? l0 + G : l0;  // (the last node: t is 0 and the difference unused)
+    const double f_law = had == kOpacityLaw ? pc.fscale[x] : 1.0;
+    double *fx = pc.ftab + static_cast<size_t>(x) * G;
+    for (int g = lane; g < G; g += 64) {
+      const double a = l0[g];
+      const double f_new = exp(fma(t, l1[g] - a, a));
+      const double f_old = had == kOpacityTable ? fx[g] : f_law;
+      fx[g] = f_new;
+      const int gl = g - pc.g_lo;
+      if (gl >= 0 && gl < pc.Gl) pc.gratio[static_cast<size_t>(gl) * pc.N + x] = f_old / f_new;
+    }
+  }
+}
+
 constexpr int kPlanckCells = 64, kPlanckGroups = 32, kPlanckThreads = 256;
-template <bool REG, bool LAW = false>
+template <bool REG, bool LAW = false, bool TAB = false>
 __global__ __launch_bounds__(kPlanckThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void planck_cells_kernel(PlanckCells pc, const double *Tc, double *B) {
   static_assert(REG || !LAW, "the opacity law is a region handle's");
+  static_assert((REG && !LAW) || !TAB, "the opacity table is a region handle's and excludes the law");
   __shared__ double tile[2][kPlanckCells * (kPlanckGroups + 1)];
   __shared__ double bsum[kPlanckThreads / 64][kPlanckCells];
   __shared__ double rk[65];
@@ -1353,13 +1413,19 @@ __global__ __launch_bounds__(kPlanckThreads) __attribute__((amdgpu_waves_per_eu(
           const size_t o = static_cast<size_t>(g0 + j) * pc.N + x0 + lane;
           double owed = pc.owed[o] + pc.dB[o] * dT;
           if constexpr (LAW) owed = owed * pc.fratio[x0 + lane];
+          if constexpr (TAB) owed = owed * pc.gratio[o];
           pay = owed > -b ? owed : -b;
           pc.owed[o] = owed - pay;
           pc.dB[o] = db;
         }
         tile[0][lane * (kPlanckGroups + 1) + j] = b;
         tile[1][lane * (kPlanckGroups + 1) + j] = b + pay;
-        bacc += sg[g0 + j] * db;
+        if constexpr (TAB) {
+          const double fg = lane < nx ? pc.ftab[static_cast<size_t>(x0 + lane) * pc.G + g] : 0.0;
+          bacc += (sg[g0 + j] * fg) * db;
+        } else {
+          bacc += sg[g0 + j] * db;
+        }
       }
       __syncthreads();
       for (int i = threadIdx.x; i < nx * ng; i += blockDim.x) {
@@ -1881,10 +1947,12 @@ __global__ __launch_bounds__(64 * kRowsWaves) void phi_correction_rows_kernel(Se
 // one wave per cell, lanes over groups, then a butterfly over the wave.  REG: sigma is
 // [nregions][Gl] and cell x reads the row of its region, sigma_g(x)
 // LAW: sigma_g(x) = sigma[region][g] fscale[x]: q and the exported b both take the cell's f
-template <bool REG, bool LAW = false>
+// TAB (the opacity table; not with LAW): sigma_g(x) = sigma[region][g] fscale[x fstride + g]
+// inside the sum; bpart is the Planck pass's sum sigma_g f_g dB_g/dT and is exported as it is
+template <bool REG, bool LAW = false, bool TAB = false>
 __global__ void material_q_kernel(const double *phi, int nparts, const double *B, const double *sigma, double W,
                                   const double *bpart, double *q, int Gl, int N, const int *cell_region,
-                                  const double *fscale) {
+                                  const double *fscale, int fstride) {
   const int lane = threadIdx.x & 63;
   const int nw = (gridDim.x * blockDim.x) >> 6;
   const size_t NG = static_cast<size_t>(N) * Gl;
@@ -1896,7 +1964,10 @@ __global__ void material_q_kernel(const double *phi, int nparts, const double *B
     for (int g = lane; g < Gl; g += 64) {
       double ph = phi[o + g];
       for (int p = 1; p < nparts; ++p) ph += phi[p * NG + o + g];
-      acc += sg[g] * (ph - W * B[o + g]);
+      if constexpr (TAB)
+        acc += (sg[g] * fscale[static_cast<size_t>(x) * fstride + g]) * (ph - W * B[o + g]);
+      else
+        acc += sg[g] * (ph - W * B[o + g]);
     }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if (lane == 0) {
@@ -1915,13 +1986,17 @@ __global__ void material_q_kernel(const double *phi, int nparts, const double *B
 // expressions unfused); dT kept for the next Planck pass's owed emission
 // S(T) = sum over ALL G groups of sigma_g B_g(T) and its derivative (rt_oracle.c
 // material_emission_all)
+// TAB (the opacity table): sigma_g f_g with the cell's row fall[g] of every group's f
+template <bool TAB = false>
 __device__ PlanckPair material_emission_all(const PlanckCells &pc, const double *sigma_all, double T,
-                                            const double *rk) {
+                                            const double *rk, const double *fall = nullptr) {
   double a = 0.0, d = 0.0;
   for (int g = 0; g < pc.G; ++g) {
     const PlanckPair v = cell_group_planck(pc, T, g, kPlanckPre, rk);
-    a += sigma_all[g] * v.b;
-    d += sigma_all[g] * v.db;
+    double sv = sigma_all[g];
+    if constexpr (TAB) sv = sv * fall[g];
+    a += sv * v.b;
+    d += sv * v.db;
   }
   return PlanckPair{a, d};
 }
@@ -1937,8 +2012,10 @@ __device__ PlanckPair material_emission_all(const PlanckCells &pc, const double 
 // REG: the cell's own heat capacity rho_cv_r[cell_region[x]] (the argument is unused) and, on
 // the Newton path, its own row of the [nregions][G] table of every group's opacity.
 // LAW: S(T') with the cell's lagged opacity, f(x) held fixed during the solve.
+// TAB (the opacity table): S(T') = sum over all G of sigma_g f_g(x) B_g(T'), the cell's row of ftab
+// held fixed during the solve.
 constexpr double kNewtonFrac = 0.25;
-template <bool REG, bool LAW = false>
+template <bool REG, bool LAW = false, bool TAB = false>
 __global__ void material_update_kernel(PlanckCells pc, double *T, const double *qb, double *dTlast, double dt,
                                        double rho_cv_one, double W, int N) {
   __shared__ double rk[65];
@@ -1964,7 +2041,9 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
       dTlast[x] = dT;
       continue;
     }
-    PlanckPair s0 = material_emission_all(pc, sigma_all, T0, rk);
+    const double *fall = nullptr;
+    if constexpr (TAB) fall = pc.ftab + static_cast<size_t>(x) * pc.G;
+    PlanckPair s0 = material_emission_all<TAB>(pc, sigma_all, T0, rk, fall);
     double f = 1.0;
     if constexpr (LAW) {
       f = pc.fscale[x];
@@ -1993,7 +2072,7 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
       }
       Tn = t;
       for (int it = 0; it < 200; ++it) {
-        PlanckPair sv = material_emission_all(pc, sigma_all, t, rk);
+        PlanckPair sv = material_emission_all<TAB>(pc, sigma_all, t, rk, fall);
         if constexpr (LAW) sv = PlanckPair{f * sv.b, f * sv.db};
         const double fv = rho_cv * (t - T0) + dt * W * sv.b - dt * A;
         if (fv > 0.0) hi = t; else lo = t;
@@ -2019,11 +2098,11 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
 // E[x] = dt W sum_gl sigma_gl ((Beff - B) + owed): the energy per volume the material owes
 // the radiation (rt_get_material_transit); one wave per cell, lanes over groups.  REG: sigma is
 // [nregions][Gl], the cell's region's row
-// LAW: times the cell's fscale[x]
-template <bool REG, bool LAW = false>
+// LAW: times the cell's fscale[x].  TAB (the opacity table): sigma_gl fscale[x fstride + gl] in the sum
+template <bool REG, bool LAW = false, bool TAB = false>
 __global__ void material_transit_kernel(const double *B, const double *Beff, const double *owed, const double *sigma,
                                         double scale, double *E, int Gl, int N, const int *cell_region,
-                                        const double *fscale) {
+                                        const double *fscale, int fstride) {
   const int lane = threadIdx.x & 63;
   const int nw = (gridDim.x * blockDim.x) >> 6;
   for (int x = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; x < N; x += nw) {
@@ -2031,8 +2110,11 @@ __global__ void material_transit_kernel(const double *B, const double *Beff, con
     const double *sg = sigma;
     if constexpr (REG) sg = sigma + static_cast<size_t>(cell_region[x]) * Gl;
     double acc = 0.0;
-    for (int g = lane; g < Gl; g += 64)
-      acc += sg[g] * ((Beff[o + g] - B[o + g]) + owed[static_cast<size_t>(g) * N + x]);
+    for (int g = lane; g < Gl; g += 64) {
+      double sv = sg[g];
+      if constexpr (TAB) sv = sv * fscale[static_cast<size_t>(x) * fstride + g];
+      acc += sv * ((Beff[o + g] - B[o + g]) + owed[static_cast<size_t>(g) * N + x]);
+    }
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
     if constexpr (LAW) acc *= fscale[x];
     if (lane == 0) E[x] = scale * acc;
@@ -2043,24 +2125,62 @@ __global__ void material_transit_kernel(const double *B, const double *Beff, con
 // in transit of cell x and group gl, (Beff - B) + owed in B units, carries the energy
 // dt W sigma_g f(x) per unit, so it is multiplied by f_old / f_new and paid again by the
 // Planck pass's rule, p = max(owed, -B): Beff = B + p, owed -= p.  One lane per cell.
+// Every transition among nothing, the law and the table (had_law: what was in force), per group:
+// to the table, opacity_table_kernel has formed f_g and gratio = f_old,g / f_new,g just before;
+// from the table, f_old,g is the cell's ftab entry and f_new the law's f(x) or 1.
 __global__ void opacity_rescale_kernel(PlanckCells pc, const double *T, int had_law) {
+  const bool to_table = pc.tab_lnf != nullptr;
   for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < pc.N; x += gridDim.x * blockDim.x) {
     double f_new = 1.0;
-    if (pc.law_n) {
+    if (!to_table && pc.law_n) {
       const int rg = pc.cell_region[x];
       f_new = opacity_scale(T[x], pc.law_Tref[rg], pc.law_n[rg], pc.law_min, pc.law_max);
     }
-    const double ratio = (had_law ? pc.fscale[x] : 1.0) / f_new;
+    const double f_cell = had_law == kOpacityLaw ? pc.fscale[x] : 1.0;
     for (int gl = 0; gl < pc.Gl; ++gl) {
 #pragma clang fp contract(off)
       const size_t o = static_cast<size_t>(gl) * pc.N + x, ob = static_cast<size_t>(x) * pc.Gl + gl;
+      double ratio;
+      if (to_table)
+        ratio = pc.gratio[o];
+      else
+        ratio = (had_law == kOpacityTable ? pc.ftab[static_cast<size_t>(x) * pc.G + pc.g_lo + gl] : f_cell) / f_new;
       const double b = pc.Bcell[ob];
       const double owed = (pc.owed[o] + (pc.Beff[ob] - b)) * ratio;
       const double pay = owed > -b ? owed : -b;
       pc.owed[o] = owed - pay;
       pc.Beff[ob] = b + pay;
     }
-    pc.fscale[x] = f_new;
+    if (!to_table && pc.fscale) pc.fscale[x] = f_new;
+  }
+}
+
+// ... and bpart with it where the table comes or goes: the table form of the Planck pass keeps
+// bpart = sum sigma_g f_g dB_g/dT with f inside the sum, the other forms the unscaled sum, so a
+// transition to or from the table forms it again from the stored dB/dT -- in the Planck pass's
+// own order (group j of a 32-group tile to wave j mod 4, the waves' sums added in turn), so that
+// a table set and cleared leaves bpart as that pass wrote it.  tab: with the cell's row of ftab.
+__global__ void opacity_bpart_kernel(PlanckCells pc, int tab) {
+  constexpr int nwave = kPlanckThreads / 64;
+  for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < pc.N; x += gridDim.x * blockDim.x) {
+    const double *sg = pc.rsigma + static_cast<size_t>(pc.cell_region[x]) * pc.Gl;
+    const double *fg = tab ? pc.ftab + static_cast<size_t>(x) * pc.G + pc.g_lo : nullptr;
+    double b = 0.0;
+    for (int w = 0; w < nwave; ++w) {
+      double bacc = 0.0;
+      for (int g0 = 0; g0 < pc.Gl; g0 += kPlanckGroups) {
+        const int ng = min(kPlanckGroups, pc.Gl - g0);
+        for (int j = w; j < ng; j += nwave) {
+          const double db = pc.dB[static_cast<size_t>(g0 + j) * pc.N + x];
+          if (tab)
+            bacc += (sg[g0 + j] * fg[g0 + j]) * db;
+          else
+            bacc += sg[g0 + j] * db;
+        }
+      }
+      b += bacc;
+    }
+    pc.bpart[x] = pc.b_scale * b;
   }
 }
 
@@ -2159,8 +2279,24 @@ hipError_t launch_walk_law(int scheme, const SegArgs &a, const WalkLaw &w, int g
   if (!a.bcell || !a.seg_first || !a.seg_region || a.Gl < 1 || a.H < 1 || a.Sg < 1 || a.Q < 1)
     return hipErrorInvalidValue;
   if (!w.fscale || !w.rsigma || !w.rdx || !w.mu) return hipErrorInvalidValue;
+  // the table form reads fscale[cell fstride + fgroup0 + group], group < Gl
+  if (w.fstride < 0 || w.fgroup0 < 0 || (w.fstride > 0 && w.fgroup0 + a.Gl > w.fstride)) return hipErrorInvalidValue;
   if (a.N < kSweepCells || a.N % kSweepCells || a.N > a.Nrow || a.Lpad != 64 * a.Q) return hipErrorInvalidValue;
   if (grid != (a.reflective ? a.Q : 2 * a.Q)) return hipErrorInvalidValue;
+  if (w.fstride > 0) {
+    switch (scheme) {
+      case SCHEME_BE:
+        hipLaunchKernelGGL((sweep_walk_law_kernel<SCHEME_BE, true>), dim3(grid), dim3(64), 0, st, a, w);
+        break;
+      case SCHEME_CN:
+        hipLaunchKernelGGL((sweep_walk_law_kernel<SCHEME_CN, true>), dim3(grid), dim3(64), 0, st, a, w);
+        break;
+      default:
+        hipLaunchKernelGGL((sweep_walk_law_kernel<SCHEME_BDF2, true>), dim3(grid), dim3(64), 0, st, a, w);
+        break;
+    }
+    return hipGetLastError();
+  }
   switch (scheme) {
     case SCHEME_BE: hipLaunchKernelGGL(sweep_walk_law_kernel<SCHEME_BE>, dim3(grid), dim3(64), 0, st, a, w); break;
     case SCHEME_CN: hipLaunchKernelGGL(sweep_walk_law_kernel<SCHEME_CN>, dim3(grid), dim3(64), 0, st, a, w); break;
@@ -2354,21 +2490,31 @@ hipError_t launch_balance_sums_regions(const double *phi, const double *rk, cons
 }
 
 hipError_t launch_group_absorption_regions(const double *phi, const double *sigma, const int *cell_region,
-                                           double *out, const Geometry &g, hipStream_t st, const double *fscale) {
+                                           double *out, const Geometry &g, hipStream_t st, const double *fscale,
+                                           int fstride) {
   const dim3 grid(grid_for(static_cast<size_t>(g.N), 256));
-  if (fscale)
+  if (fstride < 0 || (fstride > 0 && (!fscale || fstride < g.Gl))) return hipErrorInvalidValue;
+  if (fstride > 0)
+    hipLaunchKernelGGL((group_absorption_regions_kernel<false, true>), grid, dim3(256), 0, st, phi, sigma,
+                       cell_region, out, g.Gl, g.N, fscale, fstride);
+  else if (fscale)
     hipLaunchKernelGGL(group_absorption_regions_kernel<true>, grid, dim3(256), 0, st, phi, sigma, cell_region, out,
-                       g.Gl, g.N, fscale);
+                       g.Gl, g.N, fscale, fstride);
   else
     hipLaunchKernelGGL(group_absorption_regions_kernel<false>, grid, dim3(256), 0, st, phi, sigma, cell_region, out,
-                       g.Gl, g.N, fscale);
+                       g.Gl, g.N, fscale, fstride);
   return hipGetLastError();
 }
 
 hipError_t launch_planck_cells(const PlanckCells &pc, const double *T, double *B, hipStream_t st) {
   const dim3 grid(grid_for(static_cast<size_t>(pc.N), kPlanckCells));
   if (pc.fscale && !(pc.cell_region && pc.law_n && pc.law_Tref && pc.fratio)) return hipErrorInvalidValue;
-  if (pc.fscale) {
+  if (pc.ftab) {  // the opacity table: one wave per cell forms f_g(x) and the ratios, then the table form
+    if (!(pc.cell_region && pc.gratio && pc.tab_T && pc.tab_r && pc.tab_lnf && pc.tab_nT >= 2)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(opacity_table_kernel, dim3(grid_for(static_cast<size_t>(pc.N) * 64, 256)), dim3(256), 0, st, pc,
+                       T, static_cast<int>(kOpacityTable));
+    hipLaunchKernelGGL((planck_cells_kernel<true, false, true>), grid, dim3(256), 0, st, pc, T, B);
+  } else if (pc.fscale) {
     hipLaunchKernelGGL(opacity_scale_kernel, dim3(grid_for(static_cast<size_t>(pc.N), 256)), dim3(256), 0, st, pc, T);
     hipLaunchKernelGGL((planck_cells_kernel<true, true>), grid, dim3(256), 0, st, pc, T, B);
   } else if (pc.cell_region) {
@@ -2447,26 +2593,33 @@ hipError_t launch_phi_correction_rows(int scheme, const SegArgs &a, const double
 
 hipError_t launch_material_q(const double *phi, int nparts, const double *B, const double *sigma, double W,
                              const double *bpart, double *q, int Gl, int N, hipStream_t st, const int *cell_region,
-                             const double *fscale) {
+                             const double *fscale, int fstride) {
   const dim3 grid(grid_for(static_cast<size_t>(N) * 64, 256));
   if (fscale && !cell_region) return hipErrorInvalidValue;  // the law is a region handle's
-  if (fscale)
+  if (fstride < 0 || (fstride > 0 && (!fscale || fstride < Gl))) return hipErrorInvalidValue;
+  if (fstride > 0)
+    hipLaunchKernelGGL((material_q_kernel<true, false, true>), grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart,
+                       q, Gl, N, cell_region, fscale, fstride);
+  else if (fscale)
     hipLaunchKernelGGL((material_q_kernel<true, true>), grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart, q, Gl,
-                       N, cell_region, fscale);
+                       N, cell_region, fscale, fstride);
   else if (cell_region)
     hipLaunchKernelGGL(material_q_kernel<true>, grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart, q, Gl, N,
-                       cell_region, fscale);
+                       cell_region, fscale, fstride);
   else
     hipLaunchKernelGGL(material_q_kernel<false>, grid, dim3(256), 0, st, phi, nparts, B, sigma, W, bpart, q, Gl, N,
-                       cell_region, fscale);
+                       cell_region, fscale, fstride);
   return hipGetLastError();
 }
 
 hipError_t launch_material_update(const PlanckCells &pc, double *T, const double *qb, double *dTlast, double dt,
                                   double rho_cv, double W, int N, hipStream_t st) {
   const dim3 grid(grid_for(static_cast<size_t>(N), 256));
-  if (pc.fscale && !pc.cell_region) return hipErrorInvalidValue;
-  if (pc.fscale)
+  if ((pc.fscale || pc.ftab) && !pc.cell_region) return hipErrorInvalidValue;
+  if (pc.ftab)
+    hipLaunchKernelGGL((material_update_kernel<true, false, true>), grid, dim3(256), 0, st, pc, T, qb, dTlast, dt,
+                       rho_cv, W, N);
+  else if (pc.fscale)
     hipLaunchKernelGGL((material_update_kernel<true, true>), grid, dim3(256), 0, st, pc, T, qb, dTlast, dt, rho_cv, W,
                        N);
   else if (pc.cell_region)
@@ -2478,25 +2631,44 @@ hipError_t launch_material_update(const PlanckCells &pc, double *T, const double
 
 hipError_t launch_material_transit(const double *B, const double *Beff, const double *owed, const double *sigma,
                                    double scale, double *E, int Gl, int N, hipStream_t st, const int *cell_region,
-                                   const double *fscale) {
+                                   const double *fscale, int fstride) {
   const dim3 grid(grid_for(static_cast<size_t>(N) * 64, 256));
   if (fscale && !cell_region) return hipErrorInvalidValue;
-  if (fscale)
+  if (fstride < 0 || (fstride > 0 && (!fscale || fstride < Gl))) return hipErrorInvalidValue;
+  if (fstride > 0)
+    hipLaunchKernelGGL((material_transit_kernel<true, false, true>), grid, dim3(256), 0, st, B, Beff, owed, sigma,
+                       scale, E, Gl, N, cell_region, fscale, fstride);
+  else if (fscale)
     hipLaunchKernelGGL((material_transit_kernel<true, true>), grid, dim3(256), 0, st, B, Beff, owed, sigma, scale, E,
-                       Gl, N, cell_region, fscale);
+                       Gl, N, cell_region, fscale, fstride);
   else if (cell_region)
     hipLaunchKernelGGL(material_transit_kernel<true>, grid, dim3(256), 0, st, B, Beff, owed, sigma, scale, E, Gl, N,
-                       cell_region, fscale);
+                       cell_region, fscale, fstride);
   else
     hipLaunchKernelGGL(material_transit_kernel<false>, grid, dim3(256), 0, st, B, Beff, owed, sigma, scale, E, Gl, N,
-                       cell_region, fscale);
+                       cell_region, fscale, fstride);
   return hipGetLastError();
 }
 
 hipError_t launch_opacity_rescale(const PlanckCells &pc, const double *T, int had_law, hipStream_t st) {
-  if (!pc.fscale || !pc.cell_region || !pc.Bcell || (pc.law_n && !pc.law_Tref)) return hipErrorInvalidValue;
+  if (!pc.cell_region || !pc.Bcell || (pc.law_n && !pc.law_Tref)) return hipErrorInvalidValue;
+  if (had_law < kOpacityNone || had_law > kOpacityTable) return hipErrorInvalidValue;
+  if (had_law == kOpacityLaw && !pc.fscale) return hipErrorInvalidValue;
+  if (had_law == kOpacityTable && !pc.ftab) return hipErrorInvalidValue;
+  if (!pc.rsigma || !pc.owed || !pc.dB || !pc.Beff || !pc.bpart) return hipErrorInvalidValue;
+  if (pc.tab_lnf) {  // to the table: f_g(x) and the per-group ratios first
+    if (pc.law_n || !(pc.ftab && pc.gratio && pc.tab_T && pc.tab_r && pc.tab_nT >= 2)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(opacity_table_kernel, dim3(grid_for(static_cast<size_t>(pc.N) * 64, 256)), dim3(256), 0, st, pc,
+                       T, had_law);
+  } else if (!pc.fscale && (pc.law_n || had_law != kOpacityTable)) {
+    return hipErrorInvalidValue;  // the law's f(x) needs its buffer; only the table cleared does without
+  }
   hipLaunchKernelGGL(opacity_rescale_kernel, dim3(grid_for(static_cast<size_t>(pc.N), 256)), dim3(256), 0, st, pc, T,
                      had_law);
+  if (pc.tab_lnf || had_law == kOpacityTable) {  // bpart takes, or loses, the table's f_g
+    hipLaunchKernelGGL(opacity_bpart_kernel, dim3(grid_for(static_cast<size_t>(pc.N), 256)), dim3(256), 0, st, pc,
+                       pc.tab_lnf ? 1 : 0);
+  }
   return hipGetLastError();
 }
 

@@ -110,6 +110,9 @@ struct WalkLaw {
   const double *rdx;          // [nregions] cell width
   const double *mu;           // [M] direction cosines
   double c, tau, dt;          // speed of light, the substep (dt / 2 for BDF2), the step
+  // the opacity table (rt_material_set_opacity_table): fscale is then [N][fstride] over all G
+  // groups, cell-major like bcell, and a lane reads f of (cell, fgroup0 + its group).  0: the law
+  int fstride, fgroup0;
 };
 hipError_t launch_walk_law(int scheme, const SegArgs &a, const WalkLaw &w, int grid, hipStream_t st);
 // the level-split pipelined BDF2 pass (kernels_split.hip): T levels over `waves` waves
@@ -161,7 +164,8 @@ hipError_t launch_balance_sums_regions(const double *phi, const double *rk, cons
                                        hipStream_t st);
 hipError_t launch_group_absorption_regions(const double *phi, const double *sigma, const int *cell_region,
                                            double *out, const Geometry &g, hipStream_t st,
-                                           const double *fscale = nullptr);  // the opacity law's f(x)
+                                           const double *fscale = nullptr,  // the opacity law's f(x)
+                                           int fstride = 0);  // > 0, the opacity table: f_g(x) = fscale[x fstride + g]
 
 // Planck group integrals per cell (material coupling): the algorithm of
 // Planck.cpp:44-337 in double precision on the device.
@@ -198,6 +202,14 @@ struct PlanckCells {
   const double *law_n;          // [nregions] exponent
   const double *law_Tref;       // [nregions] reference temperature
   double law_min, law_max;
+  // the opacity table (rt_material_set_opacity_table; excludes the law): sigma_g(x) = rsigma
+  // f_g(x), ln f linear in ln T between the nodes and constant outside.  ftab nullptr: off
+  double *ftab;                 // [N][G] f_g(x) of ALL groups, cell-major (opacity_table_kernel)
+  double *gratio;               // [Gl][N] f_old / f_new of the handle's groups (like owed)
+  const double *tab_T;          // [tab_nT] the nodes, increasing
+  const double *tab_r;          // [tab_nT - 1] 1 / log(T_{j+1} / T_j)
+  const double *tab_lnf;        // [nregions][tab_nT][G] ln f at the nodes
+  int tab_nT;
 };
 // B[N][Gl] = B_g(T(x)) and the fields above
 hipError_t launch_planck_cells(const PlanckCells &pc, const double *T, double *B, hipStream_t st);
@@ -222,9 +234,11 @@ hipError_t launch_correction_power(int scheme, const double *map, double *pow, i
 // sum of nparts [N][Gl] arrays at phi (the fused parts, or one full phi); q[N + x] = bpart[x].
 // cell_region: sigma is [nregions][Gl] and cell x takes the row cell_region[x]
 // fscale (region form only): the opacity law's f(x) scales both q and b of cell x
+// fstride > 0 (the opacity table): f_g(x) = fscale[x fstride + g] inside the sum of q; bpart
+// already holds sum sigma_g f_g dB_g/dT (the Planck pass's table form)
 hipError_t launch_material_q(const double *phi, int nparts, const double *B, const double *sigma, double W,
                              const double *bpart, double *q, int Gl, int N, hipStream_t st,
-                             const int *cell_region = nullptr, const double *fscale = nullptr);
+                             const int *cell_region = nullptr, const double *fscale = nullptr, int fstride = 0);
 // from qb = [q, b] summed over all groups: dT = dt q / (rho_cv + dt W b), T(x) += dT, dTlast = dT
 // T += dt q / (rho_cv + dt W b), or the root of the full emission where dT > T / 4 (its owed
 // emission added there, dT 0): rt_oracle.c orc_material_update.  pc.cell_region set: rho_cv is
@@ -235,11 +249,16 @@ hipError_t launch_material_update(const PlanckCells &pc, double *T, const double
 // cell_region: as for launch_material_q
 hipError_t launch_material_transit(const double *B, const double *Beff, const double *owed, const double *sigma,
                                    double scale, double *E, int Gl, int N, hipStream_t st,
-                                   const int *cell_region = nullptr, const double *fscale = nullptr);
+                                   const int *cell_region = nullptr, const double *fscale = nullptr,
+                                   int fstride = 0);  // fstride: as for launch_material_q
 // the opacity law set, changed or cleared between steps: f_new from T (pc.fscale then holds it;
 // pc.law_n == nullptr: 1), and the emission in transit (Beff - B) + owed of every cell and group
 // times f_old / f_new, paid again as p = max(owed, -B): Beff = B + p, owed -= p.  f_old: pc.fscale,
 // or 1 where had_law is 0
+// had_law names what was in force: 0 nothing, 1 the law (pc.fscale), 2 the table (pc.ftab, per
+// group).  What comes into force is pc's: the table where pc.tab_lnf is set (f_g from T to pc.ftab
+// by opacity_table_kernel, per-group ratios), else the law where pc.law_n is set, else nothing
+enum { kOpacityNone = 0, kOpacityLaw = 1, kOpacityTable = 2 };
 hipError_t launch_opacity_rescale(const PlanckCells &pc, const double *T, int had_law, hipStream_t st);
 
 }  // namespace rtamd

@@ -285,6 +285,14 @@ struct rt_solver {
   std::vector<double> law_n, law_Tref;
   double law_min = 1.0, law_max = 1.0;
   rtsn_detail::DeviceBuf fscale, lawtab;
+  // the opacity table (rt_material_set_opacity_table; excludes the law): sigma_g(x) = rho kappa_g
+  // f_g(x).  ftab [N][G] every group's f then [Gl][N] the Planck pass's f_old / f_new; tabdev the
+  // nodes [nT], 1 / log(T_{j+1} / T_j) [nT - 1] and ln f [regions][nT][G] (device); tab_T, tab_r,
+  // tab_lnf their host copies (rt_material_stability)
+  bool table = false;
+  int tab_nT = 0;
+  std::vector<double> tab_T, tab_r, tab_lnf;
+  rtsn_detail::DeviceBuf ftab, tabdev;
   long long lane_off[4] = {-1, -1, -1, -1};
   // segment mode (long lines): the pipelined segment pass with every segment inside one region
   // (regions::plan_segments at the target Ls of segment_lines); seg_tab the kernel's tables

@@ -17,6 +17,14 @@ static rt_status unit_maps_s(rt_solver *s) {
   return line_maps_s<S>(s, true, s->map_unit, s->hmap_unit);
 }
 
+// the kernels' f argument of the temperature-dependent opacity in force: the law's f(x) [N]
+// (stride 0), the table's f_g(x) from the handle's first group on (stride G), or none
+static const double *opacity_f(const rt_solver *s) {
+  if (s->table) return static_cast<const double *>(s->ftab.p) + s->g_lo;
+  return s->law ? static_cast<const double *>(s->fscale.p) : nullptr;
+}
+static int opacity_fstride(const rt_solver *s) { return s->table ? s->p.G : 0; }
+
 static rt_status material_planck(rt_solver *s) {
   HIP_TRY(s, launch_planck_cells(s->pc, static_cast<const double *>(s->Tcell.p), static_cast<double *>(s->Bcell.p),
                                  s->stream));
@@ -25,8 +33,10 @@ static rt_status material_planck(rt_solver *s) {
 
 // dt W sum_g rho kappa_g dB_g/dT(T_max) / rho_cv over all G groups (rt_material_stability): the
 // emission's stiffness at the hottest cell, 1 / (1 + number) the Fleck factor there
-// (gt, rho_cv: the handle's own medium, or one region's)
-static double material_stability_number(const rt_solver *s, const phys::GroupTable &gt, double rho_cv, double T_max) {
+// (gt, rho_cv: the handle's own medium, or one region's; fg: nullptr, or the opacity table's f_g
+// of every group there)
+static double material_stability_number(const rt_solver *s, const phys::GroupTable &gt, double rho_cv, double T_max,
+                                        const double *fg = nullptr) {
   const int G = s->p.G;
   std::vector<double> lo(s->gt.e_edge.begin(), s->gt.e_edge.begin() + G), hi(s->gt.e_edge.begin() + 1,
                                                                              s->gt.e_edge.begin() + G + 1);
@@ -35,7 +45,7 @@ static double material_stability_number(const rt_solver *s, const phys::GroupTab
   phys::gauss_legendre(s->M_full, phys::kFourPi, mu.data(), wt.data());
   double W = 0.0, sum = 0.0;
   for (double w : wt) W += w;
-  for (int g = 0; g < G; ++g) sum += gt.rho[g] * gt.kappa[g] * dB[g] * phys::kBoltzmannJPK;
+  for (int g = 0; g < G; ++g) sum += gt.rho[g] * gt.kappa[g] * (fg ? fg[g] : 1.0) * dB[g] * phys::kBoltzmannJPK;
   return s->p.dt * W * sum / rho_cv;
 }
 
@@ -45,6 +55,25 @@ static double opacity_scale_host(const rt_solver *s, int k, double T) {
   const double v = T > 0.0 && std::isfinite(T) ? std::pow(T / s->law_Tref[k], -n)
                                                : (n > 0.0 ? s->law_max : (n < 0.0 ? s->law_min : 1.0));
   return std::min(std::max(v, s->law_min), s->law_max);
+}
+
+// the opacity table's f_g of region k at temperature T, every group (the device's
+// opacity_table_kernel, kernels.hip: the same bracket, t and fma)
+static void opacity_table_host(const rt_solver *s, int k, double T, double *f) {
+  const int nT = s->tab_nT, G = s->p.G;
+  int j = 0;
+  double t = 0.0;
+  if (T > 0.0 && std::isfinite(T) && T >= s->tab_T[0]) {
+    if (T >= s->tab_T[nT - 1]) {
+      j = nT - 1;
+    } else {
+      while (j + 2 < nT && T >= s->tab_T[j + 1]) ++j;
+      t = std::log(T / s->tab_T[j]) * s->tab_r[j];
+    }
+  }
+  const double *l0 = s->tab_lnf.data() + (static_cast<size_t>(k) * nT + j) * G;
+  const double *l1 = j + 1 < nT ? l0 + G : l0;
+  for (int g = 0; g < G; ++g) f[g] = std::exp(std::fma(t, l1[g] - l0[g], l0[g]));
 }
 
 extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
@@ -60,7 +89,13 @@ extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
       double T_max = 0.0;
       for (int c = s->first_cell[k]; c < s->first_cell[k + 1]; ++c)
         if (std::isfinite(T[c])) T_max = std::max(T_max, T[c]);
-      double number = material_stability_number(s, s->regions[k].gt, s->rho_cv_r[k], T_max);
+      std::vector<double> fg;
+      if (s->table) {  // the table's f_g there, inside the sum
+        fg.resize(s->p.G);
+        opacity_table_host(s, static_cast<int>(k), T_max, fg.data());
+      }
+      double number = material_stability_number(s, s->regions[k].gt, s->rho_cv_r[k], T_max,
+                                                s->table ? fg.data() : nullptr);
       if (s->law) number *= opacity_scale_host(s, static_cast<int>(k), T_max);  // the opacity there
       worst = std::max(worst, number);
     }
@@ -178,9 +213,12 @@ static rt_status enable_region_coupling(rt_solver *s, const double *rho_cv, cons
   pc.rsigma_all = pc.rho_cv_r + R;
   s->rho_cv_r.assign(rho_cv, rho_cv + R);
   s->rho_cv = rho_cv[0];
-  s->law = false;  // (enabled again: the opacity law is off until set)
+  s->law = s->table = false;  // (enabled again: the opacity law and table are off until set)
   pc.fscale = nullptr;
   pc.law_n = pc.law_Tref = nullptr;
+  pc.ftab = pc.gratio = nullptr;
+  pc.tab_T = pc.tab_r = pc.tab_lnf = nullptr;
+  pc.tab_nT = 0;
   if ((st = material_planck(s))) return st;
   HIP_TRY(s, hipStreamSynchronize(s->stream));  // T0 dies at return
   s->material = true;  // from here the chain is the one-step plan's (region_wave_plan)
@@ -302,7 +340,7 @@ extern "C" rt_status rt_material_sweep(rt_solver *s, double *d_q) {
     if ((st = compute_moments(s))) return st;
     HIP_TRY(s, launch_material_q(static_cast<const double *>(s->mom.p), 1, B, static_cast<const double *>(s->rmedium.p),
                                  s->wsum, bp, q, s->Gl, s->p.N, s->stream, static_cast<const int *>(s->cell_region.p),
-                                 s->law ? static_cast<const double *>(s->fscale.p) : nullptr));
+                                 opacity_f(s), opacity_fstride(s)));
     return RT_OK;
   }
   if (s->phi_fused) {
@@ -423,8 +461,7 @@ extern "C" rt_status rt_get_material_transit(rt_solver *s, double *E) {
       static_cast<const double *>(s->Bcell.p), static_cast<const double *>(s->Beff.p),
       static_cast<const double *>(s->owed.p), static_cast<const double *>(regional(s) ? s->rmedium.p : s->sigma.p),
       s->p.dt * s->wsum, static_cast<double *>(d.p), s->Gl, s->p.N, s->stream,
-      regional(s) ? static_cast<const int *>(s->cell_region.p) : nullptr,
-      s->law ? static_cast<const double *>(s->fscale.p) : nullptr);
+      regional(s) ? static_cast<const int *>(s->cell_region.p) : nullptr, opacity_f(s), opacity_fstride(s));
   if (e == hipSuccess) e = hipMemcpyAsync(E, d.p, sizeof(double) * s->p.N, hipMemcpyDeviceToHost, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   (void)hipStreamSynchronize(s->stream);
@@ -436,9 +473,9 @@ extern "C" rt_status rt_get_material_transit(rt_solver *s, double *E) {
 // ---------------------------------------------------------------------------
 // the opacity law (include/rtsn.h rt_material_set_opacity_law)
 // ---------------------------------------------------------------------------
-extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exponent, const double *T_ref,
-                                                 int nregions, double scale_min, double scale_max) {
-  const char *fn = "rt_material_set_opacity_law";
+// the handle a temperature-dependent opacity needs (rt_material_set_opacity_law and
+// rt_material_set_opacity_table share the preconditions, statuses and messages)
+static rt_status opacity_handle(rt_solver *s, const char *fn) {
   if (!s) return fail(nullptr, RT_ERR_ARG, std::string(fn) + ": NULL handle");
   if (!regional(s))
     return fail(s, RT_ERR_STATE, std::string(fn) + ": not a region handle; the law needs a region handle in segment "
@@ -448,6 +485,13 @@ extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exp
                                  "segment mode (rt_set_wavefront(s, 0), then rt_material_enable_segments)");
   if (!s->material)
     return fail(s, RT_ERR_STATE, std::string(fn) + ": call rt_material_enable_segments first");
+  return RT_OK;
+}
+
+extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exponent, const double *T_ref,
+                                                 int nregions, double scale_min, double scale_max) {
+  const char *fn = "rt_material_set_opacity_law";
+  if (rt_status st = opacity_handle(s, fn)) return st;
   const int R = static_cast<int>(s->regions.size());
   const bool off = !exponent && nregions == 0;
   if (!off) {
@@ -462,7 +506,7 @@ extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exp
     if (!(scale_min > 0.0) || !(scale_min <= scale_max) || !std::isfinite(scale_max))
       return fail(s, RT_ERR_ARG, std::string(fn) + ": need 0 < scale_min <= scale_max < infinity");
   }
-  if (off && !s->law) return RT_OK;
+  if (off && !s->law) return RT_OK;  // (also with the table on: the law is off, the table stays)
   HIP_TRY(s, hipSetDevice(s->device));
   const size_t N = s->p.N;
   if (!s->fscale.p) {
@@ -471,7 +515,8 @@ extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exp
     if (e) return fail(s, RT_ERR_NOMEM, std::string("opacity law buffers: ") + hipGetErrorString(e));
   }
   PlanckCells &pc = s->pc;
-  const int had_law = s->law ? 1 : 0;
+  // what was in force: the table is replaced by the law through the same rescale, per group
+  const int had_law = s->table ? kOpacityTable : (s->law ? kOpacityLaw : kOpacityNone);
   if (!off) {
     std::vector<double> tab(2 * R);
     std::copy(exponent, exponent + R, tab.begin());
@@ -488,16 +533,109 @@ extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exp
   }
   pc.fscale = static_cast<double *>(s->fscale.p);
   pc.fratio = pc.fscale + N;
+  pc.tab_T = pc.tab_r = pc.tab_lnf = nullptr;  // (a table in force: pc.ftab still holds its f_g, the f_old)
   // f from the current T, and the emission in transit rescaled by f_old / f_new (off: f_new = 1)
   HIP_TRY(s, launch_opacity_rescale(pc, static_cast<const double *>(s->Tcell.p), had_law, s->stream));
   s->law = !off;
+  s->table = false;
+  pc.ftab = pc.gratio = nullptr;
   if (off) pc.fscale = nullptr;  // the kernels' forms without the law again
+  return RT_OK;
+}
+
+extern "C" rt_status rt_material_set_opacity_table(rt_solver *s, const double *T_grid, int nT, const double *scale,
+                                                   int nregions) {
+  const char *fn = "rt_material_set_opacity_table";
+  if (rt_status st = opacity_handle(s, fn)) return st;
+  const int R = static_cast<int>(s->regions.size());
+  const size_t N = s->p.N, G = s->p.G;
+  const bool off = !T_grid && nT == 0 && nregions == 0;
+  if (!off) {
+    if (!T_grid || !scale) return fail(s, RT_ERR_ARG, std::string(fn) + ": NULL T_grid or scale");
+    if (nregions != R)
+      return fail(s, RT_ERR_ARG, std::string(fn) + ": nregions must be the handle's " + std::to_string(R));
+    if (nT < 2) return fail(s, RT_ERR_ARG, std::string(fn) + ": the grid needs at least 2 nodes");
+    for (int j = 0; j < nT; ++j)
+      if (!(T_grid[j] > 0.0) || !std::isfinite(T_grid[j]) || (j && !(T_grid[j] > T_grid[j - 1])))
+        return fail(s, RT_ERR_ARG, std::string(fn) + ": T_grid must be finite, > 0 and strictly increasing");
+    for (size_t i = 0; i < static_cast<size_t>(R) * nT * G; ++i)
+      if (!(scale[i] > 0.0) || !std::isfinite(scale[i]))
+        return fail(s, RT_ERR_ARG, std::string(fn) + ": every scale entry must be finite and > 0");
+  }
+  if (off && !s->table) return RT_OK;  // (also with the law on: the table is off, the law stays)
+  HIP_TRY(s, hipSetDevice(s->device));
+  if (!s->ftab.p) {  // f_g(x) of every group, then the Planck pass's f_old / f_new of the handle's
+    if (hipError_t e = dalloc(s->ftab, sizeof(double) * N * (G + s->Gl)))
+      return fail(s, RT_ERR_NOMEM, std::string("opacity table buffers: ") + hipGetErrorString(e));
+  }
+  PlanckCells &pc = s->pc;
+  const int had = s->table ? kOpacityTable : (s->law ? kOpacityLaw : kOpacityNone);
+  if (!off) {
+    // nodes, 1 / log(T_{j+1} / T_j) and ln f, formed in long double and rounded once
+    const size_t count = 2 * static_cast<size_t>(nT) - 1 + static_cast<size_t>(R) * nT * G;
+    std::vector<double> tab(count);
+    std::copy(T_grid, T_grid + nT, tab.begin());
+    for (int j = 0; j + 1 < nT; ++j)
+      tab[nT + j] = static_cast<double>(1.0L / std::log(static_cast<long double>(T_grid[j + 1]) /
+                                                        static_cast<long double>(T_grid[j])));
+    for (size_t i = 0; i < static_cast<size_t>(R) * nT * G; ++i)
+      tab[2 * nT - 1 + i] = static_cast<double>(std::log(static_cast<long double>(scale[i])));
+    if (s->tabdev.bytes < count * sizeof(double)) {
+      HIP_TRY(s, hipStreamSynchronize(s->stream));  // a smaller table may still be read
+      s->tabdev.reset();
+      if (hipError_t e = dalloc(s->tabdev, count * sizeof(double)))
+        return fail(s, RT_ERR_NOMEM, std::string("opacity table: ") + hipGetErrorString(e));
+    }
+    if (rt_status st = upload(s, s->tabdev, tab.data(), count * sizeof(double))) return st;
+    s->tab_nT = nT;
+    s->tab_T.assign(tab.begin(), tab.begin() + nT);
+    s->tab_r.assign(tab.begin() + nT, tab.begin() + 2 * nT - 1);
+    s->tab_lnf.assign(tab.begin() + 2 * nT - 1, tab.end());
+    pc.tab_T = static_cast<const double *>(s->tabdev.p);
+    pc.tab_r = pc.tab_T + nT;
+    pc.tab_lnf = pc.tab_r + (nT - 1);
+    pc.tab_nT = nT;
+  } else {
+    pc.tab_T = pc.tab_r = pc.tab_lnf = nullptr;
+    pc.tab_nT = 0;
+  }
+  pc.ftab = static_cast<double *>(s->ftab.p);
+  pc.gratio = pc.ftab + N * G;
+  pc.law_n = pc.law_Tref = nullptr;  // (a law in force: pc.fscale still holds its f(x), the f_old)
+  // f_g from the current T, the emission in transit rescaled by f_old,g / f_new,g and paid again,
+  // and bpart with or without f_g inside its sum
+  HIP_TRY(s, launch_opacity_rescale(pc, static_cast<const double *>(s->Tcell.p), had, s->stream));
+  s->table = !off;
+  s->law = false;
+  pc.fscale = pc.fratio = nullptr;
+  if (off) pc.ftab = pc.gratio = nullptr;  // the kernels' forms without the table again
+  return RT_OK;
+}
+
+extern "C" rt_status rt_get_opacity_scale_groups(rt_solver *s, double *f) {
+  if (!s || !f) return fail(s, RT_ERR_ARG, "rt_get_opacity_scale_groups: bad argument");
+  if (!s->material) return fail(s, RT_ERR_STATE, "rt_get_opacity_scale_groups: material coupling is off");
+  const size_t N = s->p.N, G = s->p.G, Gl = s->Gl;
+  if (!s->law && !s->table) {
+    std::fill(f, f + N * Gl, 1.0);
+    return RT_OK;
+  }
+  HIP_TRY(s, hipSetDevice(s->device));
+  std::vector<double> h(s->table ? N * G : N);
+  HIP_TRY(s, hipMemcpyAsync(h.data(), s->table ? s->ftab.p : s->fscale.p, sizeof(double) * h.size(),
+                            hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  for (size_t c = 0; c < N; ++c)
+    for (size_t g = 0; g < Gl; ++g) f[g + Gl * c] = s->table ? h[c * G + s->g_lo + g] : h[c];  // the law: one f per cell
   return RT_OK;
 }
 
 extern "C" rt_status rt_get_opacity_scale(rt_solver *s, double *f) {
   if (!s || !f) return fail(s, RT_ERR_ARG, "rt_get_opacity_scale: bad argument");
   if (!s->material) return fail(s, RT_ERR_STATE, "rt_get_opacity_scale: material coupling is off");
+  if (s->table)
+    return fail(s, RT_ERR_STATE, "rt_get_opacity_scale: the opacity table is on, one f per cell and group: "
+                                 "rt_get_opacity_scale_groups reads it");
   if (!s->law) {  // no law: the table opacities
     std::fill(f, f + s->p.N, 1.0);
     return RT_OK;

@@ -446,7 +446,10 @@ extern "C" rt_status rt_group_absorption_device(rt_solver *s, double *d_out) {
                                                static_cast<const double *>(s->rmedium.p),
                                                static_cast<const int *>(s->cell_region.p), d_out, geometry(s),
                                                s->stream,
-                                               s->law ? static_cast<const double *>(s->fscale.p) : nullptr));
+                                               s->table ? static_cast<const double *>(s->ftab.p) + s->g_lo
+                                               : s->law ? static_cast<const double *>(s->fscale.p)
+                                                        : nullptr,
+                                               s->table ? s->p.G : 0));
   else
     HIP_TRY(s, launch_group_absorption(static_cast<const double *>(s->mom.p), static_cast<const double *>(s->sigma.p),
                                        d_out, geometry(s), s->stream));

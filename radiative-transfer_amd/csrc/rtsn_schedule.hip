@@ -534,10 +534,12 @@ rt_status rtsn_detail::walk_coupled_pass(rt_solver *s) {
   rt_status st = event_begin(s, &e1);
   if (st) return st;
   hipError_t e;
-  if (s->law) {  // the opacity law: the constants formed per cell from sigma0 f(x), no map
+  if (s->law || s->table) {  // the opacity law or table: the constants formed per cell from sigma0 f, no map
     const size_t R = s->regions.size();
     WalkLaw w{};
-    w.fscale = static_cast<const double *>(s->fscale.p);
+    w.fscale = static_cast<const double *>(s->table ? s->ftab.p : s->fscale.p);
+    w.fstride = s->table ? s->p.G : 0;  // the table: f of (cell, group) over all G groups
+    w.fgroup0 = s->table ? s->g_lo : 0;
     w.rsigma = static_cast<const double *>(s->rmedium.p);
     w.rdx = w.rsigma + 2 * R * s->Gl;  // rmedium: rho kappa and the balance's emission [regions][Gl], then dx
     w.mu = static_cast<const double *>(s->muwt.p);

@@ -155,6 +155,8 @@ def lib():
         L.rt_material_enable_segments.argtypes = [vp, dp, C.c_int, dp]
         L.rt_material_set_opacity_law.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.c_double]
         L.rt_get_opacity_scale.argtypes = [vp, dp]
+        L.rt_material_set_opacity_table.argtypes = [vp, dp, C.c_int, dp, C.c_int]
+        L.rt_get_opacity_scale_groups.argtypes = [vp, dp]
         L.rt_material_sweep.argtypes = [vp, vp]
         L.rt_material_update.argtypes = [vp, vp]
         L.rt_material_step.argtypes = [vp, C.c_int]
@@ -642,6 +644,30 @@ class Solver:
         """(N) the opacity law's f(x) as the next coupled step uses it (1 with the law off)."""
         out = np.empty(self.N)
         _check(lib().rt_get_opacity_scale(self._h, _dp(out)), "rt_get_opacity_scale", self._h)
+        return out
+
+    def material_set_opacity_table(self, T_grid, scale):
+        """Tabulated per-group opacities (rt_material_set_opacity_table): sigma_g(x) = rho kappa_g
+        f_g(T(x)) on region k's cells, f given at the nodes T_grid (nT, increasing) as scale
+        (regions, nT, G) over all G groups of the configuration, linear in (ln T, ln f) between the
+        nodes and constant outside.  A coupled region handle in segment mode; the opacity is lagged
+        (f from T^n); the table and the power law exclude each other.  T_grid None: the table off."""
+        if T_grid is None:
+            _check(lib().rt_material_set_opacity_table(self._h, None, 0, None, 0), "rt_material_set_opacity_table",
+                   self._h)
+            return
+        tg = np.ascontiguousarray(T_grid, dtype=np.float64).ravel()
+        sc = np.ascontiguousarray(scale, dtype=np.float64)
+        if sc.ndim != 3 or sc.shape[1] != tg.size or sc.shape[2] != self.G_total:
+            raise ValueError("material_set_opacity_table: scale is (regions, len(T_grid), G) over all G groups")
+        _check(lib().rt_material_set_opacity_table(self._h, _dp(tg), int(tg.size), _dp(sc), int(sc.shape[0])),
+               "rt_material_set_opacity_table", self._h)
+
+    def opacity_scale_groups(self) -> np.ndarray:
+        """(N, G_local) f_g(x) of the handle's groups as the next coupled step uses it: ones with
+        nothing set, the power law's f(x) repeated over the groups, the table's f_g(x)."""
+        out = np.empty((self.N, self.G))  # (G: this handle's groups)
+        _check(lib().rt_get_opacity_scale_groups(self._h, _dp(out)), "rt_get_opacity_scale_groups", self._h)
         return out
 
     def material_stability(self) -> float:
