@@ -463,6 +463,64 @@ rt_status rt_material_set_opacity_table(rt_solver *s, const double *T_grid, int 
  * the next step will use it, in every state: 1 with nothing set, the law's f(x) repeated over the
  * groups, the table's f_g(x). */
 rt_status rt_get_opacity_scale_groups(rt_solver *s, double *f);
+/* A tabulated internal energy e(T) per region in place of the constant heat capacity, on ANY
+ * coupled handle (after rt_material_enable, rt_material_enable_regions or
+ * rt_material_enable_segments; RT_ERR_STATE before): region k's cells hold the material energy per
+ * volume e_k(T(x)) where they held rho_cv T (the units of rho_cv x T), so c_v = de/dT follows T.
+ * e is given at the nT nodes of T_grid (strictly increasing, finite, > 0, nT >= 2) as
+ * energy[nregions][nT], every entry finite, > 0 and strictly increasing along T; nregions must be
+ * the handle's, 1 on a handle without regions.  T_grid == NULL with nT == 0 and nregions == 0 turns
+ * the table off: the handle then uses the rho_cv it was enabled with.
+ * From the first node on -- between the nodes AND above the last -- e is linear in (ln T, ln e):
+ * with j the bracket of T (the last bracket for T >= T_{nT-1}),
+ *   t = log(T / T_j) r_j,   r_j = 1 / log(T_{j+1} / T_j),
+ *   ln e = fma(t, ln e_{j+1} - ln e_j, ln e_j),   e = exp(ln e),
+ *   c_v = de/dT = s_j e / T,   s_j = (ln e_{j+1} - ln e_j) r_j > 0:
+ * the opacity table's expression, extrapolated instead of held at the ends.  Below the first node,
+ * T <= 0 included, e = c_0 T and c_v = c_0 with c_0 = e_0 / T_0: a cold material has a constant
+ * heat capacity, e(0) = 0, and e is defined and increasing at every finite T (CN and BDF2 may step
+ * through T <= 0); the two pieces may differ by an ulp at T_0.  A T that is not finite stays so.
+ * r_j, ln e_j, s_j and c_0 are formed on the host in long double, rounded once and uploaded; log
+ * and exp run in fp64 on the device.  A two-node table with e ~ T^(beta + 1) is the power law
+ * c_v ~ T^beta above T_0 (Su-Olson: beta = 3); energy = c x T_grid is the constant heat capacity c
+ * (equal to the handle enabled with rho_cv = c to rounding, not bitwise).
+ * Step 3 with a table (q, b, A, S as above; steps 1, 2 and 4, the sweep and the all-reduce are
+ * untouched):
+ *   - T' is the root of g(T') = e(T') - e(T^n) + dt W b (T' - T^n) - dt q, one root since g
+ *     increases; q = 0 gives T' = T^n without a solve.  The linear emission is itself a root solve
+ *     because e is not linear in T.  Bracket: [T^n, e^-1(e(T^n) + dt q)] for q > 0,
+ *     [max(T^n + q / (W b), e^-1(e(T^n) + dt q)), T^n] for q < 0 (e^-1 in closed form per
+ *     bracket), verified at both ends and widened where rounding cost it; then Newton's method with
+ *     bisection from the tangent step T^n + dt q / (c_v(T^n) + dt W b).  dT = T' - T^n.
+ *   - where dT > T^n / 4 (the same test) the cell solves e(T') - e(T^n) = dt (A - W S(T')) on
+ *     [0, e^-1(e(T^n) + dt A)] instead: the constant-c_v loop with rho_cv (t - T^n) read as
+ *     e(t) - e(T^n) and rho_cv in the derivative as c_v(t); its owed emission grows by
+ *     B_g(T') - B_g(T^n) and no dB/dT dT term follows, as without a table.
+ *   - both solves stop at 1e-15 relative (the step or the bracket) or after 200 iterations; every
+ *     loop has a fixed cap.
+ * The material gains exactly dt q - dt W b dT, which the radiation and the owed emission lose: the
+ * BE energy statement holds with e in it, sum_x dx(x) (sum_g phi_g / c + e(T(x)) +
+ * rt_get_material_transit), per step to the stop rule.  rt_material_stability uses c_v at each
+ * region's hottest cell in place of rho_cv.  The opacity law and the opacity table are independent
+ * of the energy table and every combination works: both lag on T^n and are held fixed in the solve.
+ * Setting, changing or clearing the table in mid-run keeps T(x) and rescales nothing (the owed
+ * emission is the radiation's side): the material energy then changes by
+ * sum_x dx (e_new - e_old)(T(x)), which is the caller's to account for.  Set and cleared before
+ * any step, the handle is bitwise as before.  rt_material_enable* called again on a handle clears
+ * the energy table (as it clears the opacity law and table): set it again after enabling.
+ * Group and direction shards, rt_comm_material_step included, need nothing new: every rank holds
+ * the same table and the same all-reduced [q, b] and runs the same update kernel.
+ * RT_ERR_ARG, each with its own message: NULL arrays when not turning it off, nregions not the
+ * handle's, nT < 2, a grid that is not increasing, not positive or not finite, an energy entry
+ * that is not finite or <= 0, a region's energies not strictly increasing. */
+rt_status rt_material_set_energy_table(rt_solver *s, const double *T_grid, int nT, const double *energy,
+                                       int nregions);
+/* The material's internal energy per volume of every cell (N, host): e(T(x)) with the energy
+ * table, rho_cv(x) T(x) without.  Evaluated on the device by the update kernel's own function. */
+rt_status rt_get_material_energy(rt_solver *s, double *e);
+/* The heat capacity of every cell (N, host): c_v(T(x)) as the next update's first Newton step
+ * sees it, rho_cv(x) without the energy table.  Evaluated on the device like the energy. */
+rt_status rt_get_heat_capacity(rt_solver *s, double *cv);
 /* The emission's stiffness at the current T(x): number = dt W sum_g rho kappa_g
  * dB_g/dT(T_max) / rho_cv over ALL G groups (a shard reports the whole configuration's
  * number); the implicit update scales the explicit change by 1 / (1 + number) at the
@@ -483,6 +541,10 @@ rt_status rt_material_step(rt_solver *s, int nsteps);
 rt_status rt_get_temperature(rt_solver *s, double *T_cells);
 rt_status rt_get_cell_planck(rt_solver *s, double *B);
 rt_status rt_get_cell_emission(rt_solver *s, double *Beff);
+/* The last update's dT per cell (N, host): T^{n+1} - T^n where the cell took the linear emission
+ * (the dT of the next sweep's dB/dT dT term), 0 where it solved the full emission and before any
+ * update -- which of step 3's two paths each cell took. */
+rt_status rt_get_material_last_dt(rt_solver *s, double *dT);
 /* Energy per volume the material owes the radiation, per cell (N, host): dt W sum over
  * the handle's groups of sigma_g (p_g + owed_g) -- the next sweep's payment and the rest;
  * sum it over group shards. */

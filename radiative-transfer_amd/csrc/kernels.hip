@@ -1345,6 +1345,14 @@ __global__ void opacity_scale_kernel(PlanckCells pc, const double *T) {
 // kOpacityNone 1 (the last two when the table is set in mid-run, launch_opacity_rescale).
 // The owed rescale is then per (group, cell), and bpart = sum sigma_g f_g dB_g/dT with the factor
 // inside the sum: it no longer factors out, and material_q_kernel exports bpart as it is.
+// the bracket of T on a table's increasing nodes Tg[nT], nT >= 2, for T >= Tg[0]: the largest j
+// with Tg[j] <= T, the last bracket nT - 2 at most (the opacity table and the energy table)
+__device__ __forceinline__ int table_bracket(const double *Tg, int nT, double T) {
+  int j = 0;
+  while (j + 2 < nT && T >= Tg[j + 1]) ++j;
+  return j;
+}
+
 __global__ void opacity_table_kernel(PlanckCells pc, const double *T, int had) {
   const int lane = threadIdx.x & 63;
   const int nw = (gridDim.x * blockDim.x) >> 6;
@@ -1357,7 +1365,7 @@ __global__ void opacity_table_kernel(PlanckCells pc, const double *T, int had) {
       if (Tx >= pc.tab_T[nT - 1]) {
         j = nT - 1;
       } else {
-        while (j + 2 < nT && Tx >= pc.tab_T[j + 1]) ++j;
+        j = table_bracket(pc.tab_T, nT, Tx);
         t = log(Tx / pc.tab_T[j]) * pc.tab_r[j];
       }
     }
@@ -2014,10 +2022,93 @@ __device__ PlanckPair material_emission_all(const PlanckCells &pc, const double 
 // LAW: S(T') with the cell's lagged opacity, f(x) held fixed during the solve.
 // TAB (the opacity table): S(T') = sum over all G of sigma_g f_g(x) B_g(T'), the cell's row of ftab
 // held fixed during the solve.
+//
+// EOS (the energy table, PlanckCells.eos_T set; with every REG, LAW, TAB form, a plain handle on
+// region 0's row): rho_cv T becomes the region's internal energy e(T), material_energy() below.
+// The linear-emission step is then itself a root: T' solves
+//   g(T') = e(T') - e(T) + dt W b (T' - T) - dt q = 0,
+// g increasing; q = 0 leaves T.  The bracket holds by construction -- q > 0: [T, e^-1(e(T) + dt q)];
+// q < 0: [max(T + q / (W b), e^-1(e(T) + dt q)), T], each term alone taking all of dt q -- and is
+// verified, and widened a bounded number of times where rounding cost it, before the same
+// Newton-with-bisection loop as the full emission's runs from the tangent step
+// T + dt q / (c_v(T) + dt W b), by the same stop rule and cap.  Where T' - T > T / 4 (the same
+// test) the cell solves e(T') - e(T) = dt (A - W S(T')) on [0, e^-1(e(T) + dt A)]: the loop below
+// with rho_cv (t - T) read as e(t) - e(T) and rho_cv in the derivative as c_v(t).
+struct EnergyPair {
+  double e, cv;
+};
+
+// e and c_v = de/dT of region rg at temperature T: below the first node (T <= 0 and NaN too)
+// e = c_0 T, c_v = c_0; from the first node on, with j the bracket of T (the last one above the
+// last node: the chord continues), t = log(T / T_j) r_j, ln e = fma(t, ln e_{j+1} - ln e_j, ln e_j),
+// e = exp(ln e), c_v = s_j e / T -- opacity_table_kernel's expression, extrapolated
+__device__ __forceinline__ EnergyPair material_energy(const PlanckCells &pc, int rg, double T) {
+  const int nT = pc.eos_nT;
+  if (!(T >= pc.eos_T[0])) {
+    const double c0 = pc.eos_c0[rg];
+    return EnergyPair{c0 * T, c0};
+  }
+  const int j = table_bracket(pc.eos_T, nT, T);
+  const double t = log(T / pc.eos_T[j]) * pc.eos_r[j];
+  const double *le = pc.eos_lne + static_cast<size_t>(rg) * nT + j;
+  const double e = exp(fma(t, le[1] - le[0], le[0]));
+  return EnergyPair{e, pc.eos_s[static_cast<size_t>(rg) * (nT - 1) + j] * e / T};
+}
+
+// e^-1(E) of region rg, closed form per bracket: E / c_0 below the first node's energy, else
+// T_j exp((ln E - ln e_j) / s_j) with j the bracket of ln E among the ln e_j.  Used for brackets of
+// the roots only (a few ulp off the inverse of material_energy, which the solves tolerate)
+__device__ __forceinline__ double material_energy_inverse(const PlanckCells &pc, int rg, double E) {
+  const int nT = pc.eos_nT;
+  const double *le = pc.eos_lne + static_cast<size_t>(rg) * nT;
+  const double c0 = pc.eos_c0[rg];
+  if (!(E >= c0 * pc.eos_T[0])) return E / c0;
+  const double lE = log(E);
+  const int j = table_bracket(le, nT, lE);
+  return pc.eos_T[j] * exp((lE - le[j]) / pc.eos_s[static_cast<size_t>(rg) * (nT - 1) + j]);
+}
+
+// the EOS linear-emission root (see above); dT0 the tangent step.  Every loop is capped
+__device__ double material_linear_root(const PlanckCells &pc, int rg, double T0, double e0, double cv0, double q,
+                                       double dtWb, double dt) {
+  const double dtq = dt * q;
+  if (q == 0.0) return T0;
+  double tan = T0 + dtq / (cv0 + dtWb);
+  if (!(isfinite(T0) && isfinite(dtq) && isfinite(dtWb))) return tan;  // a non-finite cell stays so
+  auto g = [&](double t) { return (material_energy(pc, rg, t).e - e0) + dtWb * (t - T0) - dtq; };
+  double lo, hi;
+  if (q > 0.0) {
+    lo = T0;
+    hi = material_energy_inverse(pc, rg, e0 + dtq);
+    if (!(hi > lo)) hi = tan > lo ? tan : lo + fabs(lo) * 1e-15 + 1e-300;
+    for (int it = 0; it < 64 && g(hi) < 0.0; ++it) hi += 2.0 * (hi - lo);  // rounding cost the bracket: widen
+  } else {
+    hi = T0;
+    lo = material_energy_inverse(pc, rg, e0 + dtq);
+    if (dtWb > 0.0) lo = fmax(lo, T0 + dtq / dtWb);
+    if (!(lo < hi)) lo = tan < hi ? tan : hi - fabs(hi) * 1e-15 - 1e-300;
+    for (int it = 0; it < 64 && g(lo) > 0.0; ++it) lo -= 2.0 * (hi - lo);
+  }
+  double t = tan > lo && tan < hi ? tan : 0.5 * (lo + hi), Tn = t;
+  for (int it = 0; it < 200; ++it) {
+    const EnergyPair ev = material_energy(pc, rg, t);
+    const double fv = (ev.e - e0) + dtWb * (t - T0) - dtq;
+    if (fv > 0.0) hi = t; else lo = t;
+    double tn = t - fv / (ev.cv + dtWb);
+    if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
+    Tn = tn;
+    if (fabs(tn - t) <= 1e-15 * fabs(tn) || hi - lo <= 1e-15 * fabs(hi)) break;
+    t = tn;
+  }
+  return Tn;
+}
+
 constexpr double kNewtonFrac = 0.25;
-template <bool REG, bool LAW = false, bool TAB = false>
-__global__ void material_update_kernel(PlanckCells pc, double *T, const double *qb, double *dTlast, double dt,
-                                       double rho_cv_one, double W, int N) {
+template <bool REG, bool LAW = false, bool TAB = false, bool EOS = false>
+__global__ __launch_bounds__(EOS ? 256 : 1024) void material_update_kernel(PlanckCells pc, double *T,
+                                                                           const double *qb, double *dTlast,
+                                                                           double dt, double rho_cv_one, double W,
+                                                                           int N) {
   __shared__ double rk[65];
   if (threadIdx.x <= 64) rk[threadIdx.x] = threadIdx.x ? 1.0 / threadIdx.x : 0.0;
   __syncthreads();
@@ -2025,21 +2116,34 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
     const double q = qb[x], b = qb[N + x], T0 = T[x];
     double rho_cv = rho_cv_one;
     const double *sigma_all = pc.sigma_all;
+    int rg = 0;  // (EOS on a plain handle: region 0's row)
     if constexpr (REG) {
-      const int rg = pc.cell_region[x];
+      rg = pc.cell_region[x];
       rho_cv = pc.rho_cv_r[rg];
       sigma_all = pc.rsigma_all + static_cast<size_t>(rg) * pc.G;
     }
-    double dT;
-    {
+    double dT, e0 = 0.0;
+    if constexpr (EOS) {
+      const EnergyPair m0 = material_energy(pc, rg, T0);
+      e0 = m0.e;
+      const double Tl = material_linear_root(pc, rg, T0, m0.e, m0.cv, q, dt * W * b, dt);
+      dT = Tl - T0;
+      if (dT <= kNewtonFrac * T0) {
+        T[x] = Tl;
+        dTlast[x] = dT;
+        continue;
+      }
+    } else {
+      {
 #pragma clang fp contract(off)
-      dT = dt * q / (rho_cv + dt * W * b);
-    }
-    if (dT <= kNewtonFrac * T0) {
+        dT = dt * q / (rho_cv + dt * W * b);
+      }
+      if (dT <= kNewtonFrac * T0) {
 #pragma clang fp contract(off)
-      T[x] = T0 + dT;
-      dTlast[x] = dT;
-      continue;
+        T[x] = T0 + dT;
+        dTlast[x] = dT;
+        continue;
+      }
     }
     const double *fall = nullptr;
     if constexpr (TAB) fall = pc.ftab + static_cast<size_t>(x) * pc.G;
@@ -2050,7 +2154,11 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
       s0 = PlanckPair{f * s0.b, f * s0.db};
     }
     const double A = q + W * s0.b;
-    const double hi0 = T0 + dt * A / rho_cv;  // f(hi0) = dt W S(hi0) >= 0
+    double hi0;  // f(hi0) = dt W S(hi0) >= 0
+    if constexpr (EOS)
+      hi0 = material_energy_inverse(pc, rg, e0 + dt * A);
+    else
+      hi0 = T0 + dt * A / rho_cv;
     double Tn = hi0;
     if (hi0 > 0.0) {
       double lo = 0.0, hi = hi0, t = T0 > 0.0 && T0 < hi0 ? T0 : 0.5 * hi0;
@@ -2060,8 +2168,17 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
         const double k = dt * W * s0.b / (T0 * T0 * T0 * T0);
         double m = fmin(T0 + dT, hi0);
         for (int it = 0; it < 60; ++it) {
-          const double m2 = m * m, fm = rho_cv * (m - T0) + k * m2 * m2 - dt * A;
-          const double mn = m - fm / (rho_cv + 4.0 * k * m2 * m);
+          const double m2 = m * m;
+          double fm, dm;
+          if constexpr (EOS) {
+            const EnergyPair mv = material_energy(pc, rg, m);
+            fm = (mv.e - e0) + k * m2 * m2 - dt * A;
+            dm = mv.cv;
+          } else {
+            fm = rho_cv * (m - T0) + k * m2 * m2 - dt * A;
+            dm = rho_cv;
+          }
+          const double mn = m - fm / (dm + 4.0 * k * m2 * m);
           if (!(mn > 0.0) || fabs(mn - m) <= 1e-3 * m) {
             m = mn > 0.0 ? mn : m;
             break;
@@ -2074,9 +2191,17 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
       for (int it = 0; it < 200; ++it) {
         PlanckPair sv = material_emission_all<TAB>(pc, sigma_all, t, rk, fall);
         if constexpr (LAW) sv = PlanckPair{f * sv.b, f * sv.db};
-        const double fv = rho_cv * (t - T0) + dt * W * sv.b - dt * A;
+        double fv, dv;
+        if constexpr (EOS) {
+          const EnergyPair ev = material_energy(pc, rg, t);
+          fv = (ev.e - e0) + dt * W * sv.b - dt * A;
+          dv = ev.cv;
+        } else {
+          fv = rho_cv * (t - T0) + dt * W * sv.b - dt * A;
+          dv = rho_cv;
+        }
         if (fv > 0.0) hi = t; else lo = t;
-        double tn = t - fv / (rho_cv + dt * W * sv.db);
+        double tn = t - fv / (dv + dt * W * sv.db);
         if (!(tn > lo && tn < hi)) tn = 0.5 * (lo + hi);
         Tn = tn;
         if (fabs(tn - t) <= 1e-15 * fabs(tn) || hi - lo <= 1e-15 * hi) break;
@@ -2092,6 +2217,24 @@ __global__ void material_update_kernel(PlanckCells pc, double *T, const double *
     }
     T[x] = Tn;
     dTlast[x] = 0.0;
+  }
+}
+
+// e[x] and cv[x] at T[x] (rt_get_material_energy, rt_get_heat_capacity): the update's own
+// material_energy() with the table, rho_cv(x) T and rho_cv(x) without; one lane per cell
+__global__ void material_energy_kernel(PlanckCells pc, const double *T, double rho_cv_one, double *e, double *cv,
+                                       int N) {
+  for (int x = blockIdx.x * blockDim.x + threadIdx.x; x < N; x += gridDim.x * blockDim.x) {
+    const int rg = pc.cell_region ? pc.cell_region[x] : 0;
+    EnergyPair v;
+    if (pc.eos_T) {
+      v = material_energy(pc, rg, T[x]);
+    } else {
+      const double rho_cv = pc.cell_region ? pc.rho_cv_r[rg] : rho_cv_one;
+      v = EnergyPair{rho_cv * T[x], rho_cv};
+    }
+    if (e) e[x] = v.e;
+    if (cv) cv[x] = v.cv;
   }
 }
 
@@ -2616,6 +2759,22 @@ hipError_t launch_material_update(const PlanckCells &pc, double *T, const double
                                   double rho_cv, double W, int N, hipStream_t st) {
   const dim3 grid(grid_for(static_cast<size_t>(N), 256));
   if ((pc.fscale || pc.ftab) && !pc.cell_region) return hipErrorInvalidValue;
+  if (pc.eos_T) {  // the energy table: the EOS form of whichever form the handle runs
+    if (!(pc.eos_r && pc.eos_lne && pc.eos_s && pc.eos_c0 && pc.eos_nT >= 2)) return hipErrorInvalidValue;
+    if (pc.ftab)
+      hipLaunchKernelGGL((material_update_kernel<true, false, true, true>), grid, dim3(256), 0, st, pc, T, qb, dTlast,
+                         dt, rho_cv, W, N);
+    else if (pc.fscale)
+      hipLaunchKernelGGL((material_update_kernel<true, true, false, true>), grid, dim3(256), 0, st, pc, T, qb, dTlast,
+                         dt, rho_cv, W, N);
+    else if (pc.cell_region)
+      hipLaunchKernelGGL((material_update_kernel<true, false, false, true>), grid, dim3(256), 0, st, pc, T, qb, dTlast,
+                         dt, rho_cv, W, N);
+    else
+      hipLaunchKernelGGL((material_update_kernel<false, false, false, true>), grid, dim3(256), 0, st, pc, T, qb,
+                         dTlast, dt, rho_cv, W, N);
+    return hipGetLastError();
+  }
   if (pc.ftab)
     hipLaunchKernelGGL((material_update_kernel<true, false, true>), grid, dim3(256), 0, st, pc, T, qb, dTlast, dt,
                        rho_cv, W, N);
@@ -2626,6 +2785,15 @@ hipError_t launch_material_update(const PlanckCells &pc, double *T, const double
     hipLaunchKernelGGL(material_update_kernel<true>, grid, dim3(256), 0, st, pc, T, qb, dTlast, dt, rho_cv, W, N);
   else
     hipLaunchKernelGGL(material_update_kernel<false>, grid, dim3(256), 0, st, pc, T, qb, dTlast, dt, rho_cv, W, N);
+  return hipGetLastError();
+}
+
+hipError_t launch_material_energy(const PlanckCells &pc, const double *T, double rho_cv, double *e, double *cv, int N,
+                                  hipStream_t st) {
+  if (pc.eos_T && !(pc.eos_r && pc.eos_lne && pc.eos_s && pc.eos_c0 && pc.eos_nT >= 2)) return hipErrorInvalidValue;
+  if (pc.cell_region && !pc.rho_cv_r) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(material_energy_kernel, dim3(grid_for(static_cast<size_t>(N), 256)), dim3(256), 0, st, pc, T,
+                     rho_cv, e, cv, N);
   return hipGetLastError();
 }
 

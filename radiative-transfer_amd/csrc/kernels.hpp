@@ -210,6 +210,16 @@ struct PlanckCells {
   const double *tab_r;          // [tab_nT - 1] 1 / log(T_{j+1} / T_j)
   const double *tab_lnf;        // [nregions][tab_nT][G] ln f at the nodes
   int tab_nT;
+  // the energy table (rt_material_set_energy_table; any coupled handle, a plain one with region
+  // 0's row): the material's internal energy e_k(T) in place of rho_cv T, ln e linear in ln T
+  // between the nodes and above the last, e = c_0 T below the first (material_energy, kernels.hip).
+  // eos_T nullptr: off (the update's forms with the constant rho_cv, untouched)
+  const double *eos_T;          // [eos_nT] the nodes, increasing
+  const double *eos_r;          // [eos_nT - 1] 1 / log(T_{j+1} / T_j)
+  const double *eos_lne;        // [nregions][eos_nT] ln e at the nodes
+  const double *eos_s;          // [nregions][eos_nT - 1] (ln e_{j+1} - ln e_j) r_j > 0, the bracket's exponent
+  const double *eos_c0;         // [nregions] e_0 / T_0, the heat capacity below the first node
+  int eos_nT;
 };
 // B[N][Gl] = B_g(T(x)) and the fields above
 hipError_t launch_planck_cells(const PlanckCells &pc, const double *T, double *B, hipStream_t st);
@@ -243,8 +253,15 @@ hipError_t launch_material_q(const double *phi, int nparts, const double *B, con
 // T += dt q / (rho_cv + dt W b), or the root of the full emission where dT > T / 4 (its owed
 // emission added there, dT 0): rt_oracle.c orc_material_update.  pc.cell_region set: rho_cv is
 // the cell's region's (pc.rho_cv_r) and the argument unused
+// pc.eos_T set (the energy table): the EOS forms -- T' the root of e(T') - e(T) + dt W b (T' - T) = dt q,
+// or of e(T') - e(T) = dt (A - W S(T')) where T' - T > T / 4; rho_cv and pc.rho_cv_r are then unused
 hipError_t launch_material_update(const PlanckCells &pc, double *T, const double *qb, double *dTlast, double dt,
                                   double rho_cv, double W, int N, hipStream_t st);
+// e[x], cv[x] = the material's internal energy and heat capacity at T[x] (rt_get_material_energy,
+// rt_get_heat_capacity), by the update's own material_energy(); without the table rho_cv(x) T[x] and
+// rho_cv(x) (rho_cv: the plain handle's, as for launch_material_update).  Either output may be nullptr
+hipError_t launch_material_energy(const PlanckCells &pc, const double *T, double rho_cv, double *e, double *cv, int N,
+                                  hipStream_t st);
 // E[x] = scale sum_gl sigma[gl] ((Beff - B) + owed[gl][x]) (rt_get_material_transit);
 // cell_region: as for launch_material_q
 hipError_t launch_material_transit(const double *B, const double *Beff, const double *owed, const double *sigma,

@@ -293,6 +293,14 @@ struct rt_solver {
   int tab_nT = 0;
   std::vector<double> tab_T, tab_r, tab_lnf;
   rtsn_detail::DeviceBuf ftab, tabdev;
+  // the energy table (rt_material_set_energy_table; any coupled handle): e_k(T) in place of
+  // rho_cv T.  eosdev the nodes [nT], 1 / log(T_{j+1} / T_j) [nT - 1], ln e [regions][nT], the
+  // brackets' exponents s [regions][nT - 1] and c_0 [regions] (device); eos_tab the same doubles on
+  // the host (rt_material_stability)
+  bool eos = false;
+  int eos_nT = 0;
+  std::vector<double> eos_tab;
+  rtsn_detail::DeviceBuf eosdev;
   long long lane_off[4] = {-1, -1, -1, -1};
   // segment mode (long lines): the pipelined segment pass with every segment inside one region
   // (regions::plan_segments at the target Ls of segment_lines); seg_tab the kernel's tables

@@ -76,6 +76,20 @@ static void opacity_table_host(const rt_solver *s, int k, double T, double *f) {
   for (int g = 0; g < G; ++g) f[g] = std::exp(std::fma(t, l1[g] - l0[g], l0[g]));
 }
 
+// the energy table's c_v of region k at temperature T (the device's material_energy, kernels.hip:
+// the same bracket, t and fma); rho_cv in rt_material_stability's number with the table on
+static double heat_capacity_host(const rt_solver *s, int k, double T) {
+  const int nT = s->eos_nT, R = regional(s) ? static_cast<int>(s->regions.size()) : 1;
+  const double *Tg = s->eos_tab.data(), *r = Tg + nT, *lne = r + (nT - 1) + static_cast<size_t>(k) * nT;
+  const double *sk = r + (nT - 1) + static_cast<size_t>(R) * nT + static_cast<size_t>(k) * (nT - 1);
+  const double *c0 = r + (nT - 1) + static_cast<size_t>(R) * (2 * nT - 1);
+  if (!(T >= Tg[0])) return c0[k];
+  int j = 0;
+  while (j + 2 < nT && T >= Tg[j + 1]) ++j;
+  const double t = std::log(T / Tg[j]) * r[j];
+  return sk[j] * std::exp(std::fma(t, lne[j + 1] - lne[j], lne[j])) / T;
+}
+
 extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
   if (!s || !number) return fail(s, RT_ERR_ARG, "rt_material_stability: bad argument");
   if (!s->material) return fail(s, RT_ERR_STATE, "rt_material_stability: material coupling is off");
@@ -94,8 +108,8 @@ extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
         fg.resize(s->p.G);
         opacity_table_host(s, static_cast<int>(k), T_max, fg.data());
       }
-      double number = material_stability_number(s, s->regions[k].gt, s->rho_cv_r[k], T_max,
-                                                s->table ? fg.data() : nullptr);
+      const double cv = s->eos ? heat_capacity_host(s, static_cast<int>(k), T_max) : s->rho_cv_r[k];
+      double number = material_stability_number(s, s->regions[k].gt, cv, T_max, s->table ? fg.data() : nullptr);
       if (s->law) number *= opacity_scale_host(s, static_cast<int>(k), T_max);  // the opacity there
       worst = std::max(worst, number);
     }
@@ -105,7 +119,7 @@ extern "C" rt_status rt_material_stability(rt_solver *s, double *number) {
   double T_max = 0.0;
   for (double t : T)
     if (std::isfinite(t)) T_max = std::max(T_max, t);
-  *number = material_stability_number(s, s->gt, s->rho_cv, T_max);
+  *number = material_stability_number(s, s->gt, s->eos ? heat_capacity_host(s, 0, T_max) : s->rho_cv, T_max);
   return RT_OK;
 }
 
@@ -136,6 +150,13 @@ static void material_common(rt_solver *s) {
   phys::gauss_legendre(s->M_full, phys::kFourPi, mu_all.data(), wt_all.data());
   s->wsum_all = 0.0;
   for (double w : wt_all) s->wsum_all += w;
+}
+
+// the energy table off: the update's forms with the constant rho_cv the handle was enabled with
+static void energy_table_off(rt_solver *s) {
+  s->eos = false;
+  s->pc.eos_T = s->pc.eos_r = s->pc.eos_lne = s->pc.eos_s = s->pc.eos_c0 = nullptr;
+  s->pc.eos_nT = 0;
 }
 
 // Coupling on a slab of regions: the coupled step is the REG && CB wavefront chain (chain mode)
@@ -219,6 +240,7 @@ static rt_status enable_region_coupling(rt_solver *s, const double *rho_cv, cons
   pc.ftab = pc.gratio = nullptr;
   pc.tab_T = pc.tab_r = pc.tab_lnf = nullptr;
   pc.tab_nT = 0;
+  energy_table_off(s);  // (enabled again: the energy table is off until set)
   if ((st = material_planck(s))) return st;
   HIP_TRY(s, hipStreamSynchronize(s->stream));  // T0 dies at return
   s->material = true;  // from here the chain is the one-step plan's (region_wave_plan)
@@ -318,6 +340,7 @@ extern "C" rt_status rt_material_enable(rt_solver *s, double rho_cv, const doubl
   }
   material_common(s);
   s->rho_cv = rho_cv;
+  energy_table_off(s);  // (enabled again: the energy table is off until set)
   if ((st = material_planck(s))) return st;
   HIP_TRY(s, hipStreamSynchronize(s->stream));  // T0 dies at return
   s->material = true;
@@ -428,13 +451,13 @@ extern "C" rt_status rt_material_step(rt_solver *s, int nsteps) {
   return RT_OK;
 }
 
-// which: 0 T(x), 1 B per cell, 2 the next step's emission per cell
+// which: 0 T(x), 1 B per cell, 2 the next step's emission per cell, 3 the last update's dT per cell
 static rt_status material_fetch(rt_solver *s, int which, double *out, const char *what) {
   if (!s || !out) return fail(s, RT_ERR_ARG, std::string(what) + ": bad argument");
   if (!s->material) return fail(s, RT_ERR_STATE, std::string(what) + ": material coupling is off");
   HIP_TRY(s, hipSetDevice(s->device));
-  const size_t count = which == 0 ? s->p.N : static_cast<size_t>(s->p.N) * s->Gl;
-  const void *src = which == 0 ? s->Tcell.p : (which == 1 ? s->Bcell.p : s->Beff.p);
+  const size_t count = which == 0 || which == 3 ? s->p.N : static_cast<size_t>(s->p.N) * s->Gl;
+  const void *src = which == 0 ? s->Tcell.p : (which == 1 ? s->Bcell.p : (which == 2 ? s->Beff.p : s->dTlast.p));
   HIP_TRY(s, hipMemcpyAsync(out, src, sizeof(double) * count, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   return RT_OK;
@@ -448,6 +471,10 @@ extern "C" rt_status rt_get_cell_planck(rt_solver *s, double *B) { return materi
 
 extern "C" rt_status rt_get_cell_emission(rt_solver *s, double *Beff) {
   return material_fetch(s, 2, Beff, "rt_get_cell_emission");
+}
+
+extern "C" rt_status rt_get_material_last_dt(rt_solver *s, double *dT) {
+  return material_fetch(s, 3, dT, "rt_get_material_last_dt");
 }
 
 extern "C" rt_status rt_get_material_transit(rt_solver *s, double *E) {
@@ -644,4 +671,100 @@ extern "C" rt_status rt_get_opacity_scale(rt_solver *s, double *f) {
   HIP_TRY(s, hipMemcpyAsync(f, s->fscale.p, sizeof(double) * s->p.N, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   return RT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the energy table (include/rtsn.h rt_material_set_energy_table)
+// ---------------------------------------------------------------------------
+extern "C" rt_status rt_material_set_energy_table(rt_solver *s, const double *T_grid, int nT, const double *energy,
+                                                  int nregions) {
+  const std::string fn = "rt_material_set_energy_table";
+  if (!s) return fail(nullptr, RT_ERR_ARG, fn + ": NULL handle");
+  if (!s->material) return fail(s, RT_ERR_STATE, fn + ": material coupling is off; call rt_material_enable first");
+  const int R = regional(s) ? static_cast<int>(s->regions.size()) : 1;
+  if (!T_grid && nT == 0 && nregions == 0) {  // off: the rho_cv of rt_material_enable* again; T(x) stays
+    energy_table_off(s);
+    return RT_OK;
+  }
+  if (!T_grid || !energy) return fail(s, RT_ERR_ARG, fn + ": NULL T_grid or energy");
+  if (nregions != R) return fail(s, RT_ERR_ARG, fn + ": nregions must be the handle's " + std::to_string(R));
+  if (nT < 2) return fail(s, RT_ERR_ARG, fn + ": the grid needs at least 2 nodes");
+  for (int j = 0; j < nT; ++j)
+    if (!(T_grid[j] > 0.0) || !std::isfinite(T_grid[j]) || (j && !(T_grid[j] > T_grid[j - 1])))
+      return fail(s, RT_ERR_ARG, fn + ": T_grid must be finite, > 0 and strictly increasing");
+  for (int k = 0; k < R; ++k)
+    for (int j = 0; j < nT; ++j) {
+      const double e = energy[static_cast<size_t>(k) * nT + j];
+      if (!(e > 0.0) || !std::isfinite(e)) return fail(s, RT_ERR_ARG, fn + ": every energy entry must be finite and > 0");
+      if (j && !(e > energy[static_cast<size_t>(k) * nT + j - 1]))
+        return fail(s, RT_ERR_ARG, fn + ": every region's energy must be strictly increasing along T_grid");
+    }
+  HIP_TRY(s, hipSetDevice(s->device));
+  // nodes, r_j = 1 / log(T_{j+1} / T_j), ln e, s_j = (ln e_{j+1} - ln e_j) r_j and c_0 = e_0 / T_0, formed in long
+  // double and rounded once
+  const size_t n1 = static_cast<size_t>(nT) - 1, count = nT + n1 + static_cast<size_t>(R) * (2 * nT - 1) + R;
+  std::vector<double> tab(count);
+  std::vector<long double> rl(n1);
+  std::copy(T_grid, T_grid + nT, tab.begin());
+  for (size_t j = 0; j < n1; ++j) {
+    rl[j] = 1.0L / std::log(static_cast<long double>(T_grid[j + 1]) / static_cast<long double>(T_grid[j]));
+    tab[nT + j] = static_cast<double>(rl[j]);
+  }
+  double *lne = tab.data() + nT + n1, *sk = lne + static_cast<size_t>(R) * nT, *c0 = sk + static_cast<size_t>(R) * n1;
+  for (int k = 0; k < R; ++k) {
+    const double *e = energy + static_cast<size_t>(k) * nT;
+    for (int j = 0; j < nT; ++j) lne[static_cast<size_t>(k) * nT + j] = static_cast<double>(std::log(static_cast<long double>(e[j])));
+    for (size_t j = 0; j < n1; ++j)
+      sk[k * n1 + j] = static_cast<double>(
+          (std::log(static_cast<long double>(e[j + 1])) - std::log(static_cast<long double>(e[j]))) * rl[j]);
+    c0[k] = static_cast<double>(static_cast<long double>(e[0]) / static_cast<long double>(T_grid[0]));
+  }
+  for (size_t i = 0; i < static_cast<size_t>(R) * n1; ++i)
+    if (!(sk[i] > 0.0) || !std::isfinite(sk[i]))
+      return fail(s, RT_ERR_ARG, fn + ": every region's energy must be strictly increasing along T_grid");
+  if (s->eosdev.bytes < count * sizeof(double)) {
+    HIP_TRY(s, hipStreamSynchronize(s->stream));  // a smaller table may still be read
+    s->eosdev.reset();
+    if (hipError_t e = dalloc(s->eosdev, count * sizeof(double)))
+      return fail(s, RT_ERR_NOMEM, std::string("energy table: ") + hipGetErrorString(e));
+  }
+  if (rt_status st = upload(s, s->eosdev, tab.data(), count * sizeof(double))) return st;
+  HIP_TRY(s, hipStreamSynchronize(s->stream));  // tab dies at return
+  PlanckCells &pc = s->pc;
+  pc.eos_T = static_cast<const double *>(s->eosdev.p);
+  pc.eos_r = pc.eos_T + nT;
+  pc.eos_lne = pc.eos_r + n1;
+  pc.eos_s = pc.eos_lne + static_cast<size_t>(R) * nT;
+  pc.eos_c0 = pc.eos_s + static_cast<size_t>(R) * n1;
+  pc.eos_nT = nT;
+  s->eos_nT = nT;
+  s->eos_tab = std::move(tab);
+  s->eos = true;
+  return RT_OK;
+}
+
+// which: 0 e(T(x)), 1 c_v(T(x)), by the update's own device function
+static rt_status material_energy_fetch(rt_solver *s, int which, double *out, const char *what) {
+  if (!s || !out) return fail(s, RT_ERR_ARG, std::string(what) + ": bad argument");
+  if (!s->material) return fail(s, RT_ERR_STATE, std::string(what) + ": material coupling is off");
+  HIP_TRY(s, hipSetDevice(s->device));
+  DeviceBuf d;
+  HIP_TRY(s, dalloc(d, sizeof(double) * s->p.N));
+  double *dp = static_cast<double *>(d.p);
+  hipError_t e = launch_material_energy(s->pc, static_cast<const double *>(s->Tcell.p), s->rho_cv,
+                                        which == 0 ? dp : nullptr, which == 1 ? dp : nullptr, s->p.N, s->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d.p, sizeof(double) * s->p.N, hipMemcpyDeviceToHost, s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  (void)hipStreamSynchronize(s->stream);
+  d.reset();
+  if (e != hipSuccess) return fail(s, RT_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+  return RT_OK;
+}
+
+extern "C" rt_status rt_get_material_energy(rt_solver *s, double *e) {
+  return material_energy_fetch(s, 0, e, "rt_get_material_energy");
+}
+
+extern "C" rt_status rt_get_heat_capacity(rt_solver *s, double *cv) {
+  return material_energy_fetch(s, 1, cv, "rt_get_heat_capacity");
 }

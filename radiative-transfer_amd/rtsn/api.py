@@ -157,6 +157,9 @@ def lib():
         L.rt_get_opacity_scale.argtypes = [vp, dp]
         L.rt_material_set_opacity_table.argtypes = [vp, dp, C.c_int, dp, C.c_int]
         L.rt_get_opacity_scale_groups.argtypes = [vp, dp]
+        L.rt_material_set_energy_table.argtypes = [vp, dp, C.c_int, dp, C.c_int]
+        L.rt_get_material_energy.argtypes = [vp, dp]
+        L.rt_get_heat_capacity.argtypes = [vp, dp]
         L.rt_material_sweep.argtypes = [vp, vp]
         L.rt_material_update.argtypes = [vp, vp]
         L.rt_material_step.argtypes = [vp, C.c_int]
@@ -165,6 +168,7 @@ def lib():
         L.rt_get_material_transit.argtypes = [vp, dp]
         L.rt_get_temperature.argtypes = [vp, dp]
         L.rt_get_cell_planck.argtypes = [vp, dp]
+        L.rt_get_material_last_dt.argtypes = [vp, dp]
         L.rt_get_shard.argtypes = [vp] + [C.POINTER(C.c_int)] * 6
         L.rt_get_balance_partials.argtypes = [vp, dp, dp, dp]
         L.rt_comm_unique_id.argtypes = [C.c_char_p]
@@ -670,6 +674,40 @@ class Solver:
         _check(lib().rt_get_opacity_scale_groups(self._h, _dp(out)), "rt_get_opacity_scale_groups", self._h)
         return out
 
+    def material_set_energy_table(self, T_grid, energy):
+        """A tabulated internal energy per region in place of the constant heat capacity
+        (rt_material_set_energy_table), on any coupled handle: e_k(T) given at the nodes T_grid (nT,
+        increasing) as energy (regions, nT), > 0 and increasing along T; linear in (ln T, ln e)
+        between the nodes and above the last, e = (e_0 / T_0) T below the first.  A plain handle
+        takes one region's row.  T_grid None: the table off (the rho_cv of material_enable* again)."""
+        if T_grid is None:
+            _check(lib().rt_material_set_energy_table(self._h, None, 0, None, 0), "rt_material_set_energy_table",
+                   self._h)
+            return
+        tg = np.ascontiguousarray(T_grid, dtype=np.float64).ravel()
+        en = np.ascontiguousarray(energy, dtype=np.float64)
+        if en.ndim == 1:
+            en = en[None, :]
+        if en.ndim != 2 or en.shape[1] != tg.size:
+            raise ValueError("material_set_energy_table: energy is (regions, len(T_grid))")
+        en = np.ascontiguousarray(en)
+        _check(lib().rt_material_set_energy_table(self._h, _dp(tg), int(tg.size), _dp(en), int(en.shape[0])),
+               "rt_material_set_energy_table", self._h)
+
+    def material_energy(self) -> np.ndarray:
+        """(N) the material's internal energy per volume: e(T(x)) with the energy table,
+        rho_cv(x) T(x) without (rt_get_material_energy; evaluated on the device)."""
+        out = np.empty(self.N)
+        _check(lib().rt_get_material_energy(self._h, _dp(out)), "rt_get_material_energy", self._h)
+        return out
+
+    def heat_capacity(self) -> np.ndarray:
+        """(N) c_v(T(x)) as the next update's first Newton step sees it; rho_cv(x) without the
+        energy table (rt_get_heat_capacity)."""
+        out = np.empty(self.N)
+        _check(lib().rt_get_heat_capacity(self._h, _dp(out)), "rt_get_heat_capacity", self._h)
+        return out
+
     def material_stability(self) -> float:
         """dt W sum_g rho kappa_g dB_g/dT(T_max) / rho_cv: the emission's stiffness at the hottest
         cell (the implicit update scales the explicit change by 1 / (1 + number); < 2 was the
@@ -719,6 +757,13 @@ class Solver:
         out = np.empty(self.N * self.G)
         _check(lib().rt_get_cell_emission(self._h, _dp(out)), "rt_get_cell_emission", self._h)
         return out.reshape(self.N, self.G).T.copy()
+
+    def material_last_dT(self) -> np.ndarray:
+        """(N) the last update's dT: T' - T where the cell took the linear emission, 0 where it
+        solved the full emission and before any update (rt_get_material_last_dt)."""
+        out = np.empty(self.N)
+        _check(lib().rt_get_material_last_dt(self._h, _dp(out)), "rt_get_material_last_dt", self._h)
+        return out
 
     def material_transit(self) -> np.ndarray:
         """(N) energy per volume the material owes the radiation (rt_get_material_transit)."""
