@@ -421,7 +421,8 @@ rt_status rt_material_enable_segments(rt_solver *s, const double *rho_cv, int nr
  * With exponent 0 the results equal the map walk's to rounding, not bitwise (the maps are
  * derived in long double).  Set and cleared before any step, the handle is bitwise as before.
  * RT_ERR_STATE on a handle without regions and on a region handle in chain mode (the calls to
- * make instead: rt_create_regions, rt_set_wavefront(s, 0), rt_material_enable_segments), and on
+ * make instead: rt_create_regions, rt_set_wavefront(s, 0), rt_material_enable_segments -- or, to
+ * stay in chain mode, rt_material_set_opacity_law_chain below), and on
  * an uncoupled handle in segment mode (rt_material_enable_segments first).  RT_ERR_ARG: nregions
  * not the handle's, a T_ref that is not finite or not > 0, a non-finite exponent, bounds that
  * do not satisfy 0 < scale_min <= scale_max < infinity. */
@@ -459,6 +460,38 @@ rt_status rt_get_opacity_scale(rt_solver *s, double *f);
  * not finite, a scale entry that is not finite or <= 0, NULL arrays when not turning it off. */
 rt_status rt_material_set_opacity_table(rt_solver *s, const double *T_grid, int nT, const double *scale,
                                         int nregions);
+/* The opacity law and the opacity table on a coupled region handle in CHAIN mode (after
+ * rt_material_enable_regions; a uniform slab is a one-region handle).  As with
+ * rt_material_enable_regions / rt_material_enable_segments the handle's mode picks the call:
+ *
+ *   handle                          coupling                        law / table
+ *   region handle, chain mode       rt_material_enable_regions      rt_material_set_opacity_law_chain / _table_chain
+ *   region handle, segment mode     rt_material_enable_segments     rt_material_set_opacity_law / _table
+ *
+ * Arguments, RT_ERR_ARG rules and messages, and semantics are those of the segment-mode calls,
+ * carried by the same host code: lagging on T^n, the owed emission's rescale by f_old / f_new (per
+ * group for the table), law and table excluding and replacing each other through that rescale,
+ * turning off with NULL / 0, set and cleared before any step leaving the handle bitwise as before;
+ * rt_material_enable_regions called again clears them.  rt_get_opacity_scale(_groups),
+ * rt_material_stability, rt_get_material_transit, rt_group_absorption_device, the energy table and
+ * group shards (rt_comm_material_step) work as in segment mode.
+ * The coupled step is then one launch of the LAW FORM of the wavefront chain: no cell map; once
+ * per launch every lane forms the line constants of its cells in fp64 from sigma(x) -- the line
+ * walk's expression -- and runs the reference's cell algebra every tick.  It has 1, 2 or 4 cells
+ * per lane: lines of up to 2048 cells (1024 with the reflective left boundary) where 4 divides
+ * every region edge.  While a law or table is on the chain is planned among those (by the tick
+ * costs measured for the map form), rt_set_wavefront_cells(8) falls back to the plan's choice as
+ * any inadmissible value does, and rt_set_wavefront_waves returns RT_ERR_PARAM, nothing changed,
+ * where no such chain fits the waves.  Results do not depend on the cells per lane or the waves,
+ * bitwise; clearing the law restores the unrestricted plan.  The handle keeps its mode.
+ * RT_ERR_STATE on a handle without regions, on a segment-mode handle (the message names the
+ * segment-mode call) and on an uncoupled chain-mode handle (rt_material_enable_regions first).
+ * RT_ERR_PARAM, the handle keeping what it had, where no chain of at most 4 cells per lane divides
+ * the region edges and fits rt_set_wavefront_waves' waves (segment mode is the route then). */
+rt_status rt_material_set_opacity_law_chain(rt_solver *s, const double *exponent, const double *T_ref,
+                                            int nregions, double scale_min, double scale_max);
+rt_status rt_material_set_opacity_table_chain(rt_solver *s, const double *T_grid, int nT,
+                                              const double *scale, int nregions);
 /* f_g(x) of every cell and each of the handle's groups (N x G_local, host, f[g + G_local * c]) as
  * the next step will use it, in every state: 1 with nothing set, the law's f(x) repeated over the
  * groups, the table's f_g(x). */

@@ -133,11 +133,16 @@ hipError_t launch_fold(int KC, const FoldArgs &f, hipStream_t st);
 // and meet at a barrier every kWaveBlockTicks ticks
 constexpr int kWaveMaxWaves = 8;
 constexpr int kWaveBlockTicks = 8;
+constexpr int kLawChainCells = 4;  // the most cells per lane of the chain's law form
 struct WavePlan {
   int C, waves, lanes;
 };
 WavePlan wavefront_plan(int N, bool reflective, int max_waves);
-hipError_t launch_wavefront(int scheme, const WavePlan &p, const SegArgs &a, int nsteps, hipStream_t st);
+// law: the opacity law or table on a coupled region chain (a.lane_region and a.bcell set, nsteps 1,
+// p.C 1, 2 or 4): the law form of the chain kernels, which hold no map and form each cell's line
+// constants from sigma0 f(x) as the line walk does (WalkLaw above)
+hipError_t launch_wavefront(int scheme, const WavePlan &p, const SegArgs &a, int nsteps, hipStream_t st,
+                            const WalkLaw *law = nullptr);
 hipError_t launch_init_state(double2 *E, const double *lineB, const Geometry &g, hipStream_t st);
 // reference-layout psi / ends of the cells [c0, c0 + nc) (ends: node 0 block, then node 1)
 hipError_t launch_export_psi(const double2 *E, double *psi, const Geometry &g, int c0, int nc, hipStream_t st);

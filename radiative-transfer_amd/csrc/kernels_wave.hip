@@ -148,6 +148,88 @@ __device__ __forceinline__ void lane_emission(const SegArgs &a, int half, int el
   }
 }
 
+// A format R for the algebra of cell.hpp whose every product, quotient, sum and difference is rounded
+// on its own: fp64 with contraction off, whatever the translation unit's setting.  With plain
+// double the compiler decides per expression and per context which a * b + c * d becomes
+// fma(a, b, c * d) and which fma(c, d, a * b) (by the use counts and order of the products, which
+// change with the code around them), so the same source gives results that differ in the last
+// bits from one instantiation to the next.  The law form of the chain below
+// runs the algebra in this format: its results then do not depend on the cells per lane or the
+// waves per chain, bitwise, as the map form's do not.
+struct Unfused {
+  double v;
+  Unfused() = default;
+  __host__ __device__ constexpr Unfused(double x) : v(x) {}
+};
+#if defined(__clang__)
+#define RT_FP_CONTRACT_OFF _Pragma("clang fp contract(off)")
+#else
+#define RT_FP_CONTRACT_OFF
+#endif
+__host__ __device__ __forceinline__ Unfused operator*(Unfused a, Unfused b) {
+  RT_FP_CONTRACT_OFF
+  return Unfused(a.v * b.v);
+}
+__host__ __device__ __forceinline__ Unfused operator/(Unfused a, Unfused b) {
+  RT_FP_CONTRACT_OFF
+  return Unfused(a.v / b.v);
+}
+__host__ __device__ __forceinline__ Unfused operator+(Unfused a, Unfused b) {
+  RT_FP_CONTRACT_OFF
+  return Unfused(a.v + b.v);
+}
+__host__ __device__ __forceinline__ Unfused operator-(Unfused a, Unfused b) {
+  RT_FP_CONTRACT_OFF
+  return Unfused(a.v - b.v);
+}
+#undef RT_FP_CONTRACT_OFF
+
+// LAW (the opacity law or table in chain mode, rt_material_set_opacity_law_chain): the cell map then
+// differs from cell to cell and from step to step, so the lane holds no map.  Once per launch it
+// forms the line constants of its C cells from sigma = sigma0[region][group] f(x) and scales the
+// unit source by the cell's emission -- line_constants_unit with the arguments and the scaling of
+// the line walk's walk_law_chunk (kernels.hip) -- and every tick runs the reference algebra
+// cell_step_maybe_head on them, all of it in the format Unfused (above): the walk's expressions
+// with every operation rounded on its own, where the walk's are contracted as the compiler sees fit.  The physical cell is lane_emission's; f is fscale[x] (the law) or
+// fscale[x fstride + fgroup0 + group] (the table: a runtime choice, f is read once per launch).
+// The group and |mu| are uniform per half of the workgroup, the region per lane.  Idle lanes form
+// finite constants from the clamped cell and region 0.
+template <int C>
+__device__ __forceinline__ void lane_law_constants(const SegArgs &a, const WalkLaw &w, int half, int ell, int j, int rg,
+                                                   const double (&bc)[C], LineConstT<Unfused> (&L)[C], Unfused &hd) {
+  const int gl = min(ell / a.H, a.Gl - 1), ip = ell % a.H;
+  const double m = fabs(w.mu[half == 0 ? a.H - 1 - ip : a.H + ip]);
+  const double sig0 = w.rsigma[static_cast<size_t>(rg) * a.Gl + gl], dx = w.rdx[rg];
+  const double *fl = w.fscale + (w.fstride > 0 ? w.fgroup0 + gl : 0);
+  const size_t fs = w.fstride > 0 ? static_cast<size_t>(w.fstride) : 1;
+#pragma unroll
+  for (int c = 0; c < C; ++c) {
+    const long long kl = static_cast<long long>(j) * C + c;
+    const int k = static_cast<int>(kl < a.N - 1 ? kl : a.N - 1);
+    const double f = fl[static_cast<size_t>(half == 0 ? a.N - 1 - k : k) * fs];
+    L[c] = line_constants_unit<Unfused>(w.c, w.tau, w.dt, m, Unfused(sig0) * Unfused(f), dx);
+    L[c].c[LC_SC] = L[c].c[LC_SC] * Unfused(bc[c]);  // the unit source times the cell's emission
+  }
+  hd = Unfused(0.5) * Unfused(dx);
+}
+
+// ... and one tick of cell c on them: X -> Xn, (ein, eout) -> (oi, oo).  head: the reflective mu > 0
+// head cell (a select inside cell_step_maybe_head, so the head lane diverges from no other)
+template <int S>
+__device__ __forceinline__ void lane_law_cell(const LineConstT<Unfused> &L, Unfused hd, bool neg, bool head,
+                                              const double *X, double ein, double eout, double *Xn, double &oi,
+                                              double &oo) {
+  constexpr int K = SchemeDim<S>::K;
+  Unfused Y[K], ui, uo;
+#pragma unroll
+  for (int r = 0; r < K; ++r) Y[r] = Unfused(X[r]);
+  cell_step_maybe_head<S, Unfused>(L, hd, neg, Unfused(ein), Unfused(eout), Y, head, Unfused(X[K - 1]), ui, uo);
+#pragma unroll
+  for (int r = 0; r < K; ++r) Xn[r] = Y[r].v;
+  oi = ui.v;
+  oo = uo.v;
+}
+
 // grid: one workgroup per line (mu < 0 lines then mu > 0 lines, ell < H Gl) -- or, PAIR (the
 // reflective left boundary), one per line pair ell (chain lanes [0, Lw) the mu < 0 line,
 // [Lw, 2 Lw) its mirror).  Lw = lanes per line = ceil(N / C); the chain fills one wave.
@@ -157,9 +239,14 @@ __device__ __forceinline__ void lane_emission(const SegArgs &a, int half, int el
 // branch would make every tick divergent).
 // CB (REG only, nsteps = 1): the material-coupled step -- a.map holds the unit-B maps and the
 // lane scales their constants by its cells' emission (lane_emission); every tick is masked.
-template <int S, int C, bool PAIR, bool PAD, bool REG = false, bool CB = false>
-__global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, int Lw) {
+// LAW (CB only; LW = WalkLaw, the law's constants as a fourth kernel argument -- the other forms
+// take none, their signature and code are unchanged): no map -- the lane's own line constants
+// (lane_law_constants) and the reference algebra per tick.
+template <int S, int C, bool PAIR, bool PAD, bool REG = false, bool CB = false, bool LAW = false, class... LW>
+__global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, int Lw, LW... lw) {
   static_assert(!CB || (REG && !PAD), "the coupled step exists for region chains only");
+  static_assert(!LAW || (CB && C <= 4), "the law form exists for the coupled step, up to 4 cells per lane");
+  static_assert(sizeof...(LW) == (LAW ? 1 : 0), "the law's constants come with the law form only");
   constexpr int K = SchemeDim<S>::K, WN = map_count<S>();
   const int g = threadIdx.x & 63;  // chain lane
   const int nl = a.H * a.Gl;
@@ -193,9 +280,12 @@ __global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, in
   double W[WN], W0[WN], Wh[WN];
   int rg = 0;  // the lane's region (REG); idle lanes load region 0's map
   if constexpr (REG) rg = real ? a.lane_region[half * Lw + j] : 0;
-  head_maps<S, C, PAIR, false, REG>(a, half, ell, stride, refl_head, rg, W, W0, Wh);
+  if constexpr (!LAW) head_maps<S, C, PAIR, false, REG>(a, half, ell, stride, refl_head, rg, W, W0, Wh);
   double bc[CB ? C : 1];
   if constexpr (CB) lane_emission<C>(a, half, ell, j, bc);
+  LineConstT<Unfused> L[LAW ? C : 1];
+  Unfused hd(0.0);
+  if constexpr (LAW) lane_law_constants<C>(a, lw..., half, ell, j, rg, bc, L, hd);
 
   // Xin: the state each lane receives at its tick -- lane - 1's exit state of the same level;
   // chain lane 0's is the chain head's inflow state (solver.cpp:695-697), the mu < 0 line's
@@ -250,7 +340,9 @@ __global__ __launch_bounds__(64) void wavefront_kernel(SegArgs a, int nsteps, in
 #pragma unroll
       for (int c = 0; c < C; ++c) {
         double Xn[K], oi, oo;
-        if constexpr (CB)
+        if constexpr (LAW)
+          lane_law_cell<S>(L[c], hd, half == 0, refl_head && c == 0, X, ein[c], eout[c], Xn, oi, oo);
+        else if constexpr (CB)
           lane_cell<S, C, PAIR, false, true>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo, bc[c]);
         else
           lane_cell<S, C, PAIR, false>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo);
@@ -330,10 +422,16 @@ __device__ __forceinline__ constexpr int slot_pos(int r) {  // component r's dou
 // has the SIMD's 512 (VGPRs + AGPRs), which the reflective pair at 8 cells per lane needs
 // (256 VGPRs + 376 B of scratch under the 8-wave bound).
 // CB: the material-coupled step, as in wavefront_kernel (REG only, nsteps = 1: every block masked).
-template <int S, int C, bool PAIR, bool PAD, bool WIDE, bool REG = false, bool CB = false>
-__global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(SegArgs a, int nsteps, int Lw) {
+// LAW: as in wavefront_kernel; the constants are formed before the ring is set up, outside every
+// branch, so each wave runs the same blocks and reaches the same barriers as in the map form.
+template <int S, int C, bool PAIR, bool PAD, bool WIDE, bool REG = false, bool CB = false, bool LAW = false,
+          class... LW>
+__global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(SegArgs a, int nsteps, int Lw,
+                                                                                LW... lw) {
+  static_assert(sizeof...(LW) == (LAW ? 1 : 0), "the law's constants come with the law form only");
   constexpr int K = SchemeDim<S>::K, WN = map_count<S>();
   static_assert(!CB || (REG && !PAD), "the coupled step exists for region chains only");
+  static_assert(!LAW || (CB && C <= 4), "the law form exists for the coupled step, up to 4 cells per lane");
   static_assert(K <= kChainSlot - 1, "a slot holds the carried state");
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
@@ -370,9 +468,12 @@ __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(
   double W[WN], W0[WN], Wh[WN];
   int rg = 0;  // the lane's region (REG); idle lanes load region 0's map
   if constexpr (REG) rg = real ? a.lane_region[half * Lw + j] : 0;
-  head_maps<S, C, PAIR, REDO, REG>(a, half, ell, stride, refl_head, rg, W, W0, Wh);  // VGPR-resident maps
+  if constexpr (!LAW) head_maps<S, C, PAIR, REDO, REG>(a, half, ell, stride, refl_head, rg, W, W0, Wh);  // VGPR-resident maps
   double bc[CB ? C : 1];
   if constexpr (CB) lane_emission<C>(a, half, ell, j, bc);
+  LineConstT<Unfused> L[LAW ? C : 1];
+  Unfused hd(0.0);
+  if constexpr (LAW) lane_law_constants<C>(a, lw..., half, ell, j, rg, bc, L, hd);
   double Xin[K], X[K];
   {
     const double bv = a.bdry[static_cast<size_t>(PAIR ? 0 : half) * stride + ell];
@@ -410,7 +511,9 @@ __global__ __launch_bounds__(64 * (WIDE ? kWaveMaxWaves : 4)) void chain_kernel(
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       double Xn[K], oi, oo;
-      if constexpr (CB)
+      if constexpr (LAW)
+        lane_law_cell<S>(L[c], hd, half == 0, refl_head && c == 0, X, ein[c], eout[c], Xn, oi, oo);
+      else if constexpr (CB)
         lane_cell<S, C, PAIR, REDO, true>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo, bc[c]);
       else
         lane_cell<S, C, PAIR, REDO>(c, refl_head, W, W0, Wh, X, ein[c], eout[c], Xn, oi, oo);
@@ -563,8 +666,43 @@ static hipError_t launch_wave_regions(const WavePlan &p, const SegArgs &a, int n
   return hipGetLastError();
 }
 
+// The law form of the coupled region chain (the LAW forms of wavefront_kernel, chain_kernel): 1, 2 or 4
+// cells per lane -- at 8 a BDF2 lane's constants alone (8 x 16 doubles) are the 256 registers of a
+// 5-8-wave chain.  The kernels index fscale, rsigma, rdx and mu by these: checked here.
 template <int S, bool PAIR>
-static hipError_t launch_wave_s(const WavePlan &p, const SegArgs &a, int nsteps, int grid, hipStream_t st) {
+static hipError_t launch_wave_law(const WavePlan &p, const SegArgs &a, const WalkLaw &w, int nsteps, int grid,
+                                  hipStream_t st) {
+  const int Lw = p.lanes;
+  if (!a.lane_region || !a.bcell || nsteps != 1 || a.Gl < 1 || a.H < 1) return hipErrorInvalidValue;
+  if (a.N % p.C != 0 || Lw * p.C != a.N) return hipErrorInvalidValue;
+  if (!w.fscale || !w.rsigma || !w.rdx || !w.mu) return hipErrorInvalidValue;
+  // the table form reads fscale[cell fstride + fgroup0 + group], group < Gl
+  if (w.fstride < 0 || w.fgroup0 < 0 || (w.fstride > 0 && w.fgroup0 + a.Gl > w.fstride)) return hipErrorInvalidValue;
+  const size_t lds = sizeof(double) * kChainSlot * kChainRing * static_cast<size_t>(p.waves);
+  switch (p.C) {
+#define RT_LAW_CASE(c)                                                                                              \
+  case c:                                                                                                           \
+    if (p.waves > 4)                                                                                                \
+      hipLaunchKernelGGL((chain_kernel<S, c, PAIR, false, true, true, true, true, WalkLaw>), dim3(grid),            \
+                         dim3(64 * p.waves), lds, st, a, nsteps, Lw, w);                                            \
+    else if (p.waves > 1)                                                                                           \
+      hipLaunchKernelGGL((chain_kernel<S, c, PAIR, false, false, true, true, true, WalkLaw>), dim3(grid),           \
+                         dim3(64 * p.waves), lds, st, a, nsteps, Lw, w);                                            \
+    else                                                                                                            \
+      hipLaunchKernelGGL((wavefront_kernel<S, c, PAIR, false, true, true, true, WalkLaw>), dim3(grid), dim3(64), 0, \
+                         st, a, nsteps, Lw, w);                                                                     \
+    break;
+    RT_LAW_CASE(1) RT_LAW_CASE(2) RT_LAW_CASE(4)
+#undef RT_LAW_CASE
+    default: return hipErrorInvalidValue;  // (8 cells per lane: the plan never takes it with a law on)
+  }
+  return hipGetLastError();
+}
+
+template <int S, bool PAIR>
+static hipError_t launch_wave_s(const WavePlan &p, const SegArgs &a, int nsteps, int grid, hipStream_t st,
+                                const WalkLaw *law) {
+  if (law) return launch_wave_law<S, PAIR>(p, a, *law, nsteps, grid, st);
   if (a.lane_region)
     return a.bcell ? launch_wave_regions<S, PAIR, true>(p, a, nsteps, grid, st)
                    : launch_wave_regions<S, PAIR, false>(p, a, nsteps, grid, st);
@@ -640,7 +778,8 @@ WavePlan wavefront_plan(int N, bool reflective, int max_waves) {
   return best;  // C = 0: too long for max_waves waves (the segment pipeline)
 }
 
-hipError_t launch_wavefront(int scheme, const WavePlan &p, const SegArgs &a, int nsteps, hipStream_t st) {
+hipError_t launch_wavefront(int scheme, const WavePlan &p, const SegArgs &a, int nsteps, hipStream_t st,
+                            const WalkLaw *law) {
   const bool pair = a.reflective != 0;
   const int nl = a.H * a.Gl;
   if (p.C == 0 || p.waves < 1 || p.waves > kWaveMaxWaves || nl <= 0 || nsteps < 0) return hipErrorInvalidValue;
@@ -651,14 +790,14 @@ hipError_t launch_wavefront(int scheme, const WavePlan &p, const SegArgs &a, int
   const int grid = pair ? nl : 2 * nl;
   switch (scheme) {
     case SCHEME_BE:
-      return pair ? launch_wave_s<SCHEME_BE, true>(p, a, nsteps, grid, st)
-                  : launch_wave_s<SCHEME_BE, false>(p, a, nsteps, grid, st);
+      return pair ? launch_wave_s<SCHEME_BE, true>(p, a, nsteps, grid, st, law)
+                  : launch_wave_s<SCHEME_BE, false>(p, a, nsteps, grid, st, law);
     case SCHEME_CN:
-      return pair ? launch_wave_s<SCHEME_CN, true>(p, a, nsteps, grid, st)
-                  : launch_wave_s<SCHEME_CN, false>(p, a, nsteps, grid, st);
+      return pair ? launch_wave_s<SCHEME_CN, true>(p, a, nsteps, grid, st, law)
+                  : launch_wave_s<SCHEME_CN, false>(p, a, nsteps, grid, st, law);
     default:
-      return pair ? launch_wave_s<SCHEME_BDF2, true>(p, a, nsteps, grid, st)
-                  : launch_wave_s<SCHEME_BDF2, false>(p, a, nsteps, grid, st);
+      return pair ? launch_wave_s<SCHEME_BDF2, true>(p, a, nsteps, grid, st, law)
+                  : launch_wave_s<SCHEME_BDF2, false>(p, a, nsteps, grid, st, law);
   }
 }
 

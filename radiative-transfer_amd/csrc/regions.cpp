@@ -35,7 +35,8 @@ unsigned admissible_mask(const std::vector<int> &first_cell) {
   return mask;
 }
 
-Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, int want_C, long long nsteps) {
+Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, int want_C, long long nsteps,
+          int max_C) {
   max_waves = max_waves < 1 ? 1 : (max_waves > kWaveCostWaves ? kWaveCostWaves : max_waves);
   if (first_cell.size() < 2 || first_cell.back() < 1) return Plan{};
   const int N = first_cell.back();
@@ -45,6 +46,7 @@ Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, in
   for (int ci = 0; ci < 4; ++ci) {
     if (!(mask >> ci & 1u)) continue;
     const int C = 1 << ci, Lw = N / C;
+    if (C > max_C) continue;
     const int used = reflective ? 2 * Lw : Lw, waves = (used + 63) / 64;
     if (waves > max_waves) continue;
     if (C == want_C) return Plan{C, waves, Lw};

@@ -27,8 +27,10 @@ bool first_cells(const rt_region *r, int R, std::vector<int> &first_cell);
 // bit ci set: C = 1 << ci (1, 2, 4, 8) divides every entry of first_cell
 unsigned admissible_mask(const std::vector<int> &first_cell);
 // want_C: a caller's cells per lane, taken when admissible and fitting; else the cost table's
+// max_C: the most cells per lane the kernel has (4 for the law form of the chain, which holds each
+// cell's own line constants; want_C beyond it counts as inadmissible)
 Plan plan(const std::vector<int> &first_cell, bool reflective, int max_waves, int want_C = 0,
-          long long nsteps = 1000);
+          long long nsteps = 1000, int max_C = 8);
 // cell_region[c] for c < N
 std::vector<int> cell_table(const std::vector<int> &first_cell);
 // lane_region[half][lanes] at C cells per lane: half 1 (mu > 0) lane j holds the physical

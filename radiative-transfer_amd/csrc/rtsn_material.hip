@@ -502,23 +502,47 @@ extern "C" rt_status rt_get_material_transit(rt_solver *s, double *E) {
 // ---------------------------------------------------------------------------
 // the handle a temperature-dependent opacity needs (rt_material_set_opacity_law and
 // rt_material_set_opacity_table share the preconditions, statuses and messages)
-static rt_status opacity_handle(rt_solver *s, const char *fn) {
+// chain: the *_chain calls (a coupled region handle in chain mode; the mode picks the call, as with
+// rt_material_enable_regions / rt_material_enable_segments); seg: the segment-mode sibling's name
+static rt_status opacity_handle(rt_solver *s, const char *fn, bool chain = false, const char *seg = "") {
   if (!s) return fail(nullptr, RT_ERR_ARG, std::string(fn) + ": NULL handle");
+  if (chain) {
+    if (!regional(s))
+      return fail(s, RT_ERR_STATE, std::string(fn) + ": not a region handle; the law needs a region handle "
+                                   "(rt_create_regions, rt_material_enable_regions; a uniform slab is one region)");
+    if (s->seg_mode)
+      return fail(s, RT_ERR_STATE, std::string(fn) + ": the handle is in segment mode, which takes " + seg);
+    if (!s->material)
+      return fail(s, RT_ERR_STATE, std::string(fn) + ": call rt_material_enable_regions first");
+    return RT_OK;
+  }
   if (!regional(s))
     return fail(s, RT_ERR_STATE, std::string(fn) + ": not a region handle; the law needs a region handle in segment "
                                  "mode (rt_create_regions, rt_set_wavefront(s, 0), rt_material_enable_segments)");
   if (!s->seg_mode)
     return fail(s, RT_ERR_STATE, std::string(fn) + ": the handle is in chain mode; the law runs on the line walk of "
-                                 "segment mode (rt_set_wavefront(s, 0), then rt_material_enable_segments)");
+                                 "segment mode (rt_set_wavefront(s, 0), then rt_material_enable_segments), or on the "
+                                 "chain through " + fn + "_chain");
   if (!s->material)
     return fail(s, RT_ERR_STATE, std::string(fn) + ": call rt_material_enable_segments first");
   return RT_OK;
 }
 
-extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exponent, const double *T_ref,
-                                                 int nregions, double scale_min, double scale_max) {
-  const char *fn = "rt_material_set_opacity_law";
-  if (rt_status st = opacity_handle(s, fn)) return st;
+// chain mode: the law form of the chain has 1, 2 and 4 cells per lane (kLawChainCells), so one of
+// them must divide the region edges and fit rt_set_wavefront_waves' waves.  Checked before anything
+// changes; with a law or table already on the plan already is such a chain
+static rt_status law_chain_fits(rt_solver *s, const char *fn) {
+  if (s->law || s->table) return RT_OK;
+  if (regions::plan(s->first_cell, s->p.bc_left_indicator == 2, s->wave_max, s->wave_cells, 1, kLawChainCells).C)
+    return RT_OK;
+  return fail(s, RT_ERR_PARAM, std::string(fn) + ": no chain of 1, 2 or 4 cells per lane both divides every region edge "
+                               "and fits the handle's waves (rt_set_wavefront_waves); segment mode is the route for "
+                               "this slab (rt_set_wavefront(s, 0), rt_material_enable_segments)");
+}
+
+static rt_status set_opacity_law(rt_solver *s, const char *fn, bool chain, const double *exponent, const double *T_ref,
+                                 int nregions, double scale_min, double scale_max) {
+  if (rt_status st = opacity_handle(s, fn, chain, "rt_material_set_opacity_law")) return st;
   const int R = static_cast<int>(s->regions.size());
   const bool off = !exponent && nregions == 0;
   if (!off) {
@@ -534,6 +558,8 @@ extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exp
       return fail(s, RT_ERR_ARG, std::string(fn) + ": need 0 < scale_min <= scale_max < infinity");
   }
   if (off && !s->law) return RT_OK;  // (also with the table on: the law is off, the table stays)
+  if (chain && !off)
+    if (rt_status st = law_chain_fits(s, fn)) return st;
   HIP_TRY(s, hipSetDevice(s->device));
   const size_t N = s->p.N;
   if (!s->fscale.p) {
@@ -570,10 +596,20 @@ extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exp
   return RT_OK;
 }
 
-extern "C" rt_status rt_material_set_opacity_table(rt_solver *s, const double *T_grid, int nT, const double *scale,
-                                                   int nregions) {
-  const char *fn = "rt_material_set_opacity_table";
-  if (rt_status st = opacity_handle(s, fn)) return st;
+extern "C" rt_status rt_material_set_opacity_law(rt_solver *s, const double *exponent, const double *T_ref,
+                                                 int nregions, double scale_min, double scale_max) {
+  return set_opacity_law(s, "rt_material_set_opacity_law", false, exponent, T_ref, nregions, scale_min, scale_max);
+}
+
+extern "C" rt_status rt_material_set_opacity_law_chain(rt_solver *s, const double *exponent, const double *T_ref,
+                                                       int nregions, double scale_min, double scale_max) {
+  return set_opacity_law(s, "rt_material_set_opacity_law_chain", true, exponent, T_ref, nregions, scale_min,
+                         scale_max);
+}
+
+static rt_status set_opacity_table(rt_solver *s, const char *fn, bool chain, const double *T_grid, int nT,
+                                   const double *scale, int nregions) {
+  if (rt_status st = opacity_handle(s, fn, chain, "rt_material_set_opacity_table")) return st;
   const int R = static_cast<int>(s->regions.size());
   const size_t N = s->p.N, G = s->p.G;
   const bool off = !T_grid && nT == 0 && nregions == 0;
@@ -590,6 +626,8 @@ extern "C" rt_status rt_material_set_opacity_table(rt_solver *s, const double *T
         return fail(s, RT_ERR_ARG, std::string(fn) + ": every scale entry must be finite and > 0");
   }
   if (off && !s->table) return RT_OK;  // (also with the law on: the table is off, the law stays)
+  if (chain && !off)
+    if (rt_status st = law_chain_fits(s, fn)) return st;
   HIP_TRY(s, hipSetDevice(s->device));
   if (!s->ftab.p) {  // f_g(x) of every group, then the Planck pass's f_old / f_new of the handle's
     if (hipError_t e = dalloc(s->ftab, sizeof(double) * N * (G + s->Gl)))
@@ -637,6 +675,16 @@ extern "C" rt_status rt_material_set_opacity_table(rt_solver *s, const double *T
   pc.fscale = pc.fratio = nullptr;
   if (off) pc.ftab = pc.gratio = nullptr;  // the kernels' forms without the table again
   return RT_OK;
+}
+
+extern "C" rt_status rt_material_set_opacity_table(rt_solver *s, const double *T_grid, int nT, const double *scale,
+                                                   int nregions) {
+  return set_opacity_table(s, "rt_material_set_opacity_table", false, T_grid, nT, scale, nregions);
+}
+
+extern "C" rt_status rt_material_set_opacity_table_chain(rt_solver *s, const double *T_grid, int nT,
+                                                         const double *scale, int nregions) {
+  return set_opacity_table(s, "rt_material_set_opacity_table_chain", true, T_grid, nT, scale, nregions);
 }
 
 extern "C" rt_status rt_get_opacity_scale_groups(rt_solver *s, double *f) {

@@ -81,9 +81,11 @@ rt_status rtsn_detail::upload_segment_tables(rt_solver *s) {
 }
 
 WavePlan rtsn_detail::region_wave_plan(const rt_solver *s, int wave_max) {
-  // a coupled handle only ever launches one step: the chain is planned for that (regions.hpp)
+  // a coupled handle only ever launches one step: the chain is planned for that (regions.hpp);
+  // with the opacity law or table on, among the law form's 1, 2 and 4 cells per lane -- by the tick
+  // costs measured for the map form (nobody has measured a law tick: DESIGN.md §9)
   const regions::Plan p = regions::plan(s->first_cell, s->p.bc_left_indicator == 2, wave_max, s->wave_cells,
-                                        s->material ? 1 : 1000);
+                                        s->material ? 1 : 1000, (s->law || s->table) ? kLawChainCells : 8);
   return WavePlan{p.C, p.waves, p.lanes};
 }
 

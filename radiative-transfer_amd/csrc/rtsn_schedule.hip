@@ -485,9 +485,28 @@ rt_status rtsn_detail::wave_flush(rt_solver *s) {
   return RT_OK;
 }
 
+// The opacity law or table of a coupled region handle as the sweeps take it (the line walk and the
+// law form of the chain alike): the constants are formed per cell from sigma0 f, no map
+static WalkLaw walk_law(const rt_solver *s) {
+  const size_t R = s->regions.size();
+  WalkLaw w{};
+  w.fscale = static_cast<const double *>(s->table ? s->ftab.p : s->fscale.p);
+  w.fstride = s->table ? s->p.G : 0;  // the table: f of (cell, group) over all G groups
+  w.fgroup0 = s->table ? s->g_lo : 0;
+  w.rsigma = static_cast<const double *>(s->rmedium.p);
+  w.rdx = w.rsigma + 2 * R * s->Gl;  // rmedium: rho kappa and the balance's emission [regions][Gl], then dx
+  w.mu = static_cast<const double *>(s->muwt.p);
+  w.c = phys::kLight;
+  w.dt = s->p.dt;
+  w.tau = s->p.ts_method == 3 ? s->p.dt / 2.0 : s->p.dt;
+  return w;
+}
+
 // The material-coupled step of a region handle: one launch of the REG && CB chain (the unit-B
 // maps, one set per region, their constants scaled by each cell's emission Beff), one step --
 // the stored state read once and written once; the caller has finalized (nothing queued).
+// With the opacity law or table on (rt_material_set_opacity_*_chain) the law form of the chain,
+// which the plan then keeps to 1, 2 or 4 cells per lane (region_wave_plan).
 rt_status rtsn_detail::wave_coupled_pass(rt_solver *s) {
   const WavePlan wp = wave_plan(s);
   int ci = 0;
@@ -503,7 +522,13 @@ rt_status rtsn_detail::wave_coupled_pass(rt_solver *s) {
   hipEvent_t e1;
   rt_status st = event_begin(s, &e1);
   if (st) return st;
-  const hipError_t e = launch_wavefront(s->scheme, wp, a, 1, s->stream);
+  hipError_t e;
+  if (s->law || s->table) {
+    const WalkLaw w = walk_law(s);
+    e = launch_wavefront(s->scheme, wp, a, 1, s->stream, &w);
+  } else {
+    e = launch_wavefront(s->scheme, wp, a, 1, s->stream);
+  }
   if (e != hipSuccess) {
     event_abort(s, e1);
     return fail(s, RT_ERR_DEVICE, std::string("coupled wavefront launch: ") + hipGetErrorString(e));
@@ -535,17 +560,7 @@ rt_status rtsn_detail::walk_coupled_pass(rt_solver *s) {
   if (st) return st;
   hipError_t e;
   if (s->law || s->table) {  // the opacity law or table: the constants formed per cell from sigma0 f, no map
-    const size_t R = s->regions.size();
-    WalkLaw w{};
-    w.fscale = static_cast<const double *>(s->table ? s->ftab.p : s->fscale.p);
-    w.fstride = s->table ? s->p.G : 0;  // the table: f of (cell, group) over all G groups
-    w.fgroup0 = s->table ? s->g_lo : 0;
-    w.rsigma = static_cast<const double *>(s->rmedium.p);
-    w.rdx = w.rsigma + 2 * R * s->Gl;  // rmedium: rho kappa and the balance's emission [regions][Gl], then dx
-    w.mu = static_cast<const double *>(s->muwt.p);
-    w.c = phys::kLight;
-    w.dt = s->p.dt;
-    w.tau = s->p.ts_method == 3 ? s->p.dt / 2.0 : s->p.dt;
+    const WalkLaw w = walk_law(s);
     e = launch_walk_law(s->scheme, a, w, (a.reflective ? 1 : 2) * s->Q, s->stream);
   } else {
     e = launch_walk(s->scheme, a, (a.reflective ? 1 : 2) * s->Q, s->stream);

@@ -154,8 +154,10 @@ def lib():
         L.rt_material_enable_regions.argtypes = [vp, dp, C.c_int, dp]
         L.rt_material_enable_segments.argtypes = [vp, dp, C.c_int, dp]
         L.rt_material_set_opacity_law.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.c_double]
+        L.rt_material_set_opacity_law_chain.argtypes = [vp, dp, dp, C.c_int, C.c_double, C.c_double]
         L.rt_get_opacity_scale.argtypes = [vp, dp]
         L.rt_material_set_opacity_table.argtypes = [vp, dp, C.c_int, dp, C.c_int]
+        L.rt_material_set_opacity_table_chain.argtypes = [vp, dp, C.c_int, dp, C.c_int]
         L.rt_get_opacity_scale_groups.argtypes = [vp, dp]
         L.rt_material_set_energy_table.argtypes = [vp, dp, C.c_int, dp, C.c_int]
         L.rt_get_material_energy.argtypes = [vp, dp]
@@ -633,16 +635,23 @@ class Solver:
         """sigma_g(x) = rho kappa_g f(x), f = clamp((T / T_ref[k])^(-exponent[k]), scale_min,
         scale_max) per cell of region k (rt_material_set_opacity_law): a coupled region handle in
         segment mode; the opacity is lagged (f from T^n).  exponent None: the law off."""
+        self._set_opacity_law("rt_material_set_opacity_law", exponent, T_ref, scale_min, scale_max)
+
+    def material_set_opacity_law_chain(self, exponent, T_ref, scale_min: float, scale_max: float):
+        """material_set_opacity_law on a coupled region handle in chain mode
+        (rt_material_set_opacity_law_chain; the coupled step is then the law form of the chain)."""
+        self._set_opacity_law("rt_material_set_opacity_law_chain", exponent, T_ref, scale_min, scale_max)
+
+    def _set_opacity_law(self, fn: str, exponent, T_ref, scale_min: float, scale_max: float):
+        call = getattr(lib(), fn)
         if exponent is None:
-            _check(lib().rt_material_set_opacity_law(self._h, None, None, 0, float(scale_min), float(scale_max)),
-                   "rt_material_set_opacity_law", self._h)
+            _check(call(self._h, None, None, 0, float(scale_min), float(scale_max)), fn, self._h)
             return
         n = np.ascontiguousarray(exponent, dtype=np.float64).ravel()
         tr = np.ascontiguousarray(T_ref, dtype=np.float64).ravel()
         if tr.size != n.size:
             raise ValueError("material_set_opacity_law: one exponent and one T_ref per region")
-        _check(lib().rt_material_set_opacity_law(self._h, _dp(n), _dp(tr), int(n.size), float(scale_min),
-                                                 float(scale_max)), "rt_material_set_opacity_law", self._h)
+        _check(call(self._h, _dp(n), _dp(tr), int(n.size), float(scale_min), float(scale_max)), fn, self._h)
 
     def opacity_scale(self) -> np.ndarray:
         """(N) the opacity law's f(x) as the next coupled step uses it (1 with the law off)."""
@@ -656,16 +665,23 @@ class Solver:
         (regions, nT, G) over all G groups of the configuration, linear in (ln T, ln f) between the
         nodes and constant outside.  A coupled region handle in segment mode; the opacity is lagged
         (f from T^n); the table and the power law exclude each other.  T_grid None: the table off."""
+        self._set_opacity_table("rt_material_set_opacity_table", T_grid, scale)
+
+    def material_set_opacity_table_chain(self, T_grid, scale):
+        """material_set_opacity_table on a coupled region handle in chain mode
+        (rt_material_set_opacity_table_chain; the coupled step is then the law form of the chain)."""
+        self._set_opacity_table("rt_material_set_opacity_table_chain", T_grid, scale)
+
+    def _set_opacity_table(self, fn: str, T_grid, scale):
+        call = getattr(lib(), fn)
         if T_grid is None:
-            _check(lib().rt_material_set_opacity_table(self._h, None, 0, None, 0), "rt_material_set_opacity_table",
-                   self._h)
+            _check(call(self._h, None, 0, None, 0), fn, self._h)
             return
         tg = np.ascontiguousarray(T_grid, dtype=np.float64).ravel()
         sc = np.ascontiguousarray(scale, dtype=np.float64)
         if sc.ndim != 3 or sc.shape[1] != tg.size or sc.shape[2] != self.G_total:
             raise ValueError("material_set_opacity_table: scale is (regions, len(T_grid), G) over all G groups")
-        _check(lib().rt_material_set_opacity_table(self._h, _dp(tg), int(tg.size), _dp(sc), int(sc.shape[0])),
-               "rt_material_set_opacity_table", self._h)
+        _check(call(self._h, _dp(tg), int(tg.size), _dp(sc), int(sc.shape[0])), fn, self._h)
 
     def opacity_scale_groups(self) -> np.ndarray:
         """(N, G_local) f_g(x) of the handle's groups as the next coupled step uses it: ones with
